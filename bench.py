@@ -16,6 +16,12 @@ an RCCL all-to-all of the layer-2 rows the rank's train rows read (a training
 halo, negotiated once), an all-gather of the compact train-row gradient and an
 all-reduce of the weight gradients.  W untimed warm-up epochs, then exactly K timed epochs
 bracketed by barrier + device synchronize; the MAX time over ranks is reported.
+
+A plain run sets up, warms up, times the K epochs and prints the result line
+(``ms_per_step``: milliseconds per timed epoch; ``train_loss``: the last timed
+epoch's own loss).  ``--dump-outputs DIR`` also writes what that last epoch
+computed as DIR/<name>.npy.  ``--full`` adds the evaluation pass after the timed
+epochs (``val_acc`` / ``test_acc``), the only part of the metric a plain run skips.
 """
 import argparse
 import importlib.util
@@ -38,6 +44,27 @@ def _launcher():
     return mod
 
 METRIC = "epochs/sec + val-acc, 2-layer GCN ogbn-products, 1/2/4/8 MI355X"
+
+
+def _dump_outputs(path, tr, rank):
+    """What the last timed epoch handed back, as ``path/<name>.npy`` (float32, about
+    0.6 MB at hidden 256): ``train_stats`` -- the four loss / accuracy sums
+    ``train_step()`` returns (``GCNTrainer.evaluate`` names them), summed over ranks --
+    and the state it wrote: the flat gradient, the parameters after the Adam step and
+    both Adam moments (W1, b1, W2, b2 in that order).  Same arguments, same seed: same
+    graph, weights and dropout masks, so two builds can be compared array for array."""
+    import numpy as np
+    stats = tr.last_stats[:4].clone()
+    if tr.multi:
+        import torch.distributed as dist
+        dist.all_reduce(stats)
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    arrays = {"train_stats": stats, "grads": tr.grads, "params": tr.params,
+              "adam_m": tr.m, "adam_v": tr.v}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def main():
@@ -69,9 +96,20 @@ def main():
     ap.add_argument("--shared-gpu", action="store_true",
                     help="rehearsal: every rank on cuda:0 with gloo collectives (exercises the multi-rank "
                          "HIP path on a one-GPU box; timings are not a scaling measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the evaluation pass after the "
+                         "timed epochs (val_acc / test_acc in the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed epochs write what the last one returned and updated (its loss / "
+                         "accuracy sums, the gradients, the parameters and the Adam moments) as "
+                         "DIR/<name>.npy, float32 (rank 0; identical on every rank)")
     a = ap.parse_args()
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    if a.warmup < 0:
+        ap.error("--warmup must be >= 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: start the N ranks here (children re-run this script)
         sys.exit(_launcher().spawn_ranks(a.gpus, [os.path.abspath(__file__)] + sys.argv[1:]))
@@ -160,8 +198,12 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    res = tr.evaluate()
-    train_loss = tr.train_loss()
+    train_loss = tr.train_loss()               # read from the last timed epoch's own sums
+    if a.dump_outputs:
+        _dump_outputs(a.dump_outputs, tr, rank)
+    # the evaluation pass (a forward over every row, without dropout) is not part of the
+    # headline figure
+    res = tr.evaluate() if a.full else None
 
     n, m, F, C, _, _ = SHAPES[a.dataset]
     if rank == 0:
@@ -193,15 +235,17 @@ def main():
                        # training epochs aggregate layer 2 at the rows the loss reads
                        "train_layer2_rows": "all" if tr._l2 is None else "train",
                        "train_layer1_rows": "all" if tr._l1 is None else "train-neighbours"},
-            "val_acc": round(res["val_acc"], 4),
-            "test_acc": round(res["test_acc"], 4),
             "train_loss": round(train_loss, 5),
-            "epochs_trained": a.warmup + a.steps,
+            "epochs_trained": tr.epoch,            # counted by the trainer: warm-up + timed
             "setup_s": round(setup_s, 2),
             "trainer_setup_s": round(trainer_setup_s, 2),
-            "acc_note": "synthetic-task accuracy (label/feature noise set its ceiling); not comparable "
-                        "with real ogbn-products accuracy",
+            "full": bool(a.full),
         }
+        if res is not None:
+            out["val_acc"] = round(res["val_acc"], 4)
+            out["test_acc"] = round(res["test_acc"], 4)
+            out["acc_note"] = ("synthetic-task accuracy (label/feature noise set its ceiling); not "
+                               "comparable with real ogbn-products accuracy")
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

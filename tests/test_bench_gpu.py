@@ -20,7 +20,7 @@ def _run(nproc):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["OMP_NUM_THREADS"] = "4"
     args = [sys.executable, "bench.py", "--gpus", str(nproc), "--steps", "4", "--warmup", "2",
-            "--scale", "0.02"]
+            "--scale", "0.02", "--full"]
     if nproc > 1:
         args.append("--shared-gpu")
     res = subprocess.run(args, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
