@@ -705,14 +705,17 @@ __global__ __launch_bounds__(256) void relu_dropout_bwd_kernel(
 // weight decay, over one flat fp32 parameter buffer.  t = *step + 1.  done (optional,
 // zero): the block whose arrival is counted last stores *step = t and re-zeroes *done.
 // Every block has read *step into a register before its arrival (the barrier waits for
-// the load), so no fence is needed -- only the count.
+// the load), so no fence is needed -- only the count.  The stored count is the integer
+// read plus one, not the float t the powers take: from 2^24 on, float(s + 1) rounds
+// back to s and a counter stored from it would stop.
 __global__ void gnn_adam_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
                                 const float* __restrict__ g, int n, float lr, float b1, float b2,
                                 float eps, float wd, int* __restrict__ step, unsigned* __restrict__ done,
                                 int step_done) {
   // step_done: *step was already advanced for this update (a slab_sum bump), t = *step
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const float t = (float)(*step + (step_done ? 0 : 1));
+  const int s = *step;
+  const float t = (float)(s + (step_done ? 0 : 1));
   if (i < n) {
     const float gi = g[i];
     const float mi = b1 * m[i] + (1.f - b1) * gi;
@@ -726,7 +729,7 @@ __global__ void gnn_adam_kernel(float* __restrict__ p, float* __restrict__ m, fl
   if (!done) return;
   __syncthreads();
   if (threadIdx.x == 0 && atomicAdd(done, 1u) == gridDim.x - 1) {
-    *step = (int)t;
+    *step = s + 1;
     *done = 0u;
   }
 }

@@ -36,6 +36,22 @@ def dtype_code(dt) -> int:
     return _DT_CODE[dt]
 
 
+_ONE_ID = {}
+
+
+def _nonempty_ids(col):
+    """``col``, or for a graph with no edges a one-element id buffer (kept per device):
+    the gathers issue their first column-id load unconditionally at a clamped address
+    (gnn_gather.h, gather_sum), and an empty tensor's pointer is null.  The id (0) is
+    never used -- no edge loop runs."""
+    if col.numel():
+        return col
+    buf = _ONE_ID.get(col.device)
+    if buf is None:
+        buf = _ONE_ID[col.device] = torch.zeros(1, dtype=torch.int32, device=col.device)
+    return buf
+
+
 def spmm(rowptr, col, X, F, rscale=None, bias=None, relu=False, out=None, out_dtype=torch.bfloat16,
          ld_out=None, unit_col=-1, init=None, cscale=None, init_rows=None, short_rows=None):
     """Y[i,:F] = act(rscale[i] * (init[i] + sum_{j in N(i)} cscale[j] X[j,:F]) + bias); X is [*, ldx].
@@ -62,7 +78,7 @@ def spmm(rowptr, col, X, F, rscale=None, bias=None, relu=False, out=None, out_dt
         checks.rows(cscale, X.shape[0], "spmm cscale")
     if X.is_cuda:
         hip = native.hip()
-        hip.gnn_spmm(rowptr.data_ptr(), col.data_ptr(), X.data_ptr(), out.data_ptr(),
+        hip.gnn_spmm(rowptr.data_ptr(), _nonempty_ids(col).data_ptr(), X.data_ptr(), out.data_ptr(),
                      rscale.data_ptr() if rscale is not None else 0,
                      bias.data_ptr() if bias is not None else 0, n, F, X.shape[1], out.shape[1],
                      dtype_code(X.dtype), dtype_code(out.dtype), int(relu), int(unit_col),
@@ -110,7 +126,9 @@ def spmm_fan(rowptr, col, X, F, max_deg, rscale=None, out=None):
         checks.rows(rscale, n, "spmm_fan rscale")
         if n > 0 and int((rowptr[1:] - rowptr[:-1]).max()) > max_deg:
             raise ValueError("spmm_fan: a row has more than max_deg = %d entries" % max_deg)
-    native.hip().gnn_spmm_fan(rowptr.data_ptr(), col.data_ptr(), X.data_ptr(), out.data_ptr(),
+    # (the pipelined kernel reads col through a descriptor of nnz records, but a bound
+    # above 8 or a wide row falls back to the CSR SpMM and its unconditional first load)
+    native.hip().gnn_spmm_fan(rowptr.data_ptr(), _nonempty_ids(col).data_ptr(), X.data_ptr(), out.data_ptr(),
                               rscale.data_ptr() if rscale is not None else 0, n, F, X.shape[1], out.shape[1],
                               X.shape[0], col.numel(), int(max_deg), _st(X))
     return out
@@ -124,11 +142,14 @@ class EllImage:
     (-1 past its end), or {-2, e0, e1, -1...} for a row of more than 8 entries (its CSR
     range); ``long_rows``: int32 [n_long], the ids of those rows, ascending (the GPU
     sums them in a launch of their own, so the short-row loop has no data-dependent
-    inner loop)."""
-    __slots__ = ("ell", "long_rows", "n_long")
+    inner loop); ``long_buf``: the buffer whose pointer the GPU launch gets -- ``long_rows``,
+    or one unused element when there is none (an empty tensor's pointer is null, which the
+    launcher reads as "no list" and answers with the one-shot kernel)."""
+    __slots__ = ("ell", "long_rows", "n_long", "long_buf")
 
     def __init__(self, ell, long_rows):
         self.ell, self.long_rows, self.n_long = ell, long_rows, int(long_rows.numel())
+        self.long_buf = long_rows if self.n_long else torch.zeros(1, dtype=torch.int32, device=long_rows.device)
 
     @property
     def n(self):
@@ -157,9 +178,11 @@ def ell_image(rowptr, col):
     return EllImage(ell, long_rows)
 
 
-def spmm_ell(img, col, X, F, rscale=None, out=None):
+def spmm_ell(img, col, X, F, rscale=None, out=None, oneshot=False):
     """Y[i,:F] = rscale[i] * sum_{j in N(i)} X[j,:F] from an :class:`EllImage` (bf16,
-    F <= 64; the same sums as ``spmm`` over the CSR the image was built from)."""
+    F <= 64; the same sums as ``spmm`` over the CSR the image was built from).
+    ``oneshot`` (GPU): the one-shot kernel (the launcher's choice for tables of 2^31
+    bytes or more) instead of the pipelined one; bit-identical."""
     ell = img.ell
     n = ell.shape[0]
     if out is None:
@@ -167,7 +190,8 @@ def spmm_ell(img, col, X, F, rscale=None, out=None):
     if X.is_cuda:
         native.hip().gnn_spmm_ell(ell.data_ptr(), col.data_ptr(), X.data_ptr(), out.data_ptr(),
                                   rscale.data_ptr() if rscale is not None else 0, n, F, X.shape[1],
-                                  out.shape[1], X.shape[0], img.long_rows.data_ptr(), img.n_long, _st(X))
+                                  out.shape[1], X.shape[0], 0 if oneshot else img.long_buf.data_ptr(),
+                                  img.n_long, _st(X))
         return out
     acc = torch.zeros(n, F, dtype=torch.float32)
     short = ell[:, 0] != -2                    # a long row's slots hold its CSR range
@@ -233,8 +257,9 @@ def spmm_ce(rowptr, col, Z, C, rscale, bias, labels, mask, inv_count, mode=0, G=
             G = torch.empty(n, ld, dtype=torch.bfloat16, device=Z.device)
         if gslot is not None and gslot.dtype != torch.int32:
             raise TypeError("gslot must be int32")
-        hip.gnn_spmm_ce(rowptr.data_ptr(), col.data_ptr(), Z.data_ptr(), rscale.data_ptr(), bias.data_ptr(),
-                        labels.data_ptr(), mask.data_ptr(), stats.data_ptr(), G.data_ptr() if G is not None else 0,
+        hip.gnn_spmm_ce(rowptr.data_ptr(), _nonempty_ids(col).data_ptr(), Z.data_ptr(), rscale.data_ptr(),
+                        bias.data_ptr(), labels.data_ptr(), mask.data_ptr(), stats.data_ptr(),
+                        G.data_ptr() if G is not None else 0,
                         init.data_ptr() if init is not None else 0, init.shape[1] if init is not None else 0,
                         n, C, ld, mode, float(inv_count), _st(Z),
                         gslot.data_ptr() if gslot is not None else 0, int(n_long))
