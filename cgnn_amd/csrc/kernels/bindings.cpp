@@ -67,6 +67,10 @@ int gnn_launch_spmm(const int*, const int*, const void*, void*, const float*, co
                     int, int, int, int, int, int, int, const float*, int, const float*, int, int, hipStream_t);
 int gnn_launch_spmm_fan(const int*, const int*, const void*, void*, const float*, int, int, int, int, long, long, int,
                         hipStream_t);
+int gnn_launch_wspmm(const int*, const int*, const float*, const int*, const void*, void*, const float*, const float*,
+                     const float*, int, int, int, int, int, int, int, hipStream_t);
+int gnn_launch_sddmm(const int*, const int*, const void*, const void*, float*, const float*, const float*, int, int,
+                     int, int, int, hipStream_t);
 int gnn_launch_spmm_ce(const int*, const int*, const void*, const float*, const float*,
                        const int*, const uint8_t*, float*, void*, const float*, int, int, int, int, int, float,
                        const int*, int, hipStream_t);
@@ -299,6 +303,26 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("n_rows"), py::arg("F"), py::arg("ld_x"), py::arg("ld_y"), py::arg("x_bf16"), py::arg("y_bf16"),
      py::arg("relu"), py::arg("unit_col"), py::arg("st"), py::arg("init") = 0, py::arg("ldi") = 0,
      py::arg("cscale") = 0, py::arg("init_rows") = -1, py::arg("short_rows") = 0);
+  // edge-weighted aggregate and its edge-value gradient (gnn_wspmm.hip)
+  m.def("gnn_wspmm", [](uint64_t rowptr, uint64_t col, uint64_t val, uint64_t eperm, uint64_t x, uint64_t y,
+                        uint64_t rscale, uint64_t cscale, uint64_t bias, int n_rows, int F, int ld_x, int ld_y,
+                        int x_type, int y_type, int relu, uint64_t st) {
+    chk(gnn_launch_wspmm(Pt<const int>(rowptr), Pt<const int>(col), Pt<const float>(val), Pt<const int>(eperm),
+                         Pt<const void>(x), Pt<void>(y), Pt<const float>(rscale), Pt<const float>(cscale),
+                         Pt<const float>(bias), n_rows, F, ld_x, ld_y, x_type, y_type, relu, S(st)),
+        "gnn_wspmm");
+  }, py::arg("rowptr"), py::arg("col"), py::arg("val"), py::arg("eperm"), py::arg("x"), py::arg("y"),
+     py::arg("rscale"), py::arg("cscale"), py::arg("bias"), py::arg("n_rows"), py::arg("F"), py::arg("ld_x"),
+     py::arg("ld_y"), py::arg("x_type"), py::arg("y_type"), py::arg("relu"), py::arg("st"));
+  m.def("gnn_sddmm", [](uint64_t rowptr, uint64_t col, uint64_t a, uint64_t b, uint64_t out, uint64_t rscale,
+                        uint64_t cscale, int n_rows, int F, int ld_a, int ld_b, int type, uint64_t st) {
+    chk(gnn_launch_sddmm(Pt<const int>(rowptr), Pt<const int>(col), Pt<const void>(a), Pt<const void>(b),
+                         Pt<float>(out), Pt<const float>(rscale), Pt<const float>(cscale), n_rows, F, ld_a, ld_b,
+                         type, S(st)),
+        "gnn_sddmm");
+  }, py::arg("rowptr"), py::arg("col"), py::arg("a"), py::arg("b"), py::arg("out"), py::arg("rscale"),
+     py::arg("cscale"), py::arg("n_rows"), py::arg("F"), py::arg("ld_a"), py::arg("ld_b"), py::arg("type"),
+     py::arg("st"));
   m.def("gnn_spmm_fan", [](uint64_t rowptr, uint64_t col, uint64_t x, uint64_t y, uint64_t rscale, int n_rows, int F,
                            int ldx, int ldy, long n_x_rows, long nnz, int max_deg, uint64_t st) {
     chk(gnn_launch_spmm_fan(Pt<const int>(rowptr), Pt<const int>(col), Pt<const void>(x), Pt<void>(y),

@@ -1,0 +1,389 @@
+// GNN track (beyond the reference): edge-weighted message passing for MI355X.
+//
+//   wspmm_kernel  Y[i,:F] = act( rscale[i] * sum_{e in row i} val[p(e)] * cscale[col[e]] * X[col[e],:F] + bias )
+//                 CSR aggregate with one caller-supplied fp32 value per edge; p(e) = eperm[e]
+//                 when an edge permutation is given (the backward runs over the transposed
+//                 CSR and reads the forward's value array in place), else e.
+//   sddmm_kernel  out[e] = rscale[i] * cscale[j] * sum_{f<F} A[i,f] * B[j,f]  for every edge
+//                 e = (i, j) of the CSR: the gradient of the weighted aggregate with respect
+//                 to each edge value.
+//
+// Mapping (gnn_sparse.hip's): wave64, a sub-group of L lanes owns one row, each lane owns 8
+// consecutive features (one 16-byte load per gathered bf16 / fp16 row), L = 8 / 16 / 32 / 64
+// for widths up to 64 / 128 / 256 / 512; wider rows run as 512-column slabs in the
+// launchers.  The ids and values of a chunk of L edges come with one coalesced load per
+// lane, requested one chunk ahead, and are broadcast inside the sub-group; eight gathered
+// rows are in flight per lane.  Accumulation is fp32.
+//
+// Determinism: per row and feature the multiply-adds are ONE chain of fmaf in edge order
+// (wspmm), and per edge the products are one fmaf chain per lane followed by a fixed
+// exchange tree over the L lanes (sddmm).  Neither depends on the grid, on the other rows
+// of the launch or on the run: outputs are bit-identical from run to run, and a row's
+// result is the same in any launch that holds it.  No atomics.
+//
+// Empty inputs: a row with e0 == e1 dereferences none of col / val / eperm / cscale (every
+// edge load sits behind the row's e1 > e0 test and is clamped into [e0, e1)), so a graph
+// without edges may pass null pointers for them.
+#include "cgnn_common.h"
+#include "gnn_gather.h"
+#include <algorithm>
+
+using namespace cgnn;
+using namespace cgnn::gather;
+
+namespace {
+
+// 8 features at element offset `off` as raw registers: one 16-byte load for bf16 / fp16
+// (b unused), two for fp32
+template <int XT>
+struct Raw8 {
+  uint4 a, b;
+};
+
+template <int XT>
+__device__ __forceinline__ Raw8<XT> load_raw8(const void* X, size_t off) {
+  Raw8<XT> r;
+  if (XT == 0) {
+    const uint4* p = reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(X) + off);
+    r.a = p[0];
+    r.b = p[1];
+  } else {
+    r.a = load_raw16(X, off);
+    r.b = r.a;
+  }
+  return r;
+}
+
+template <int XT>
+__device__ __forceinline__ void raw8_to_f32(const Raw8<XT>& r, float* f) {
+  if (XT == 1) {
+    bf16x8_to_f32(r.a, f);
+  } else if (XT == 2) {
+    const f16x8 v = __builtin_bit_cast(f16x8, r.a);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) f[q] = (float)v[q];
+  } else {
+    f[0] = __uint_as_float(r.a.x); f[1] = __uint_as_float(r.a.y);
+    f[2] = __uint_as_float(r.a.z); f[3] = __uint_as_float(r.a.w);
+    f[4] = __uint_as_float(r.b.x); f[5] = __uint_as_float(r.b.y);
+    f[6] = __uint_as_float(r.b.z); f[7] = __uint_as_float(r.b.w);
+  }
+}
+
+// v of lane k + u of the sub-group, u = 0..N-1 (k a multiple of N).  L = 16: the sub-group
+// is one DPP row, the ids move by row broadcast (a VALU move, no LDS permute)
+template <int L, int N>
+__device__ __forceinline__ void sub_bcast(int v, int sub_base, int k, int* out) {
+  if (L == 16 && N == 8) {
+    if (k == 0) row_bcast8<0>(v, out);
+    else row_bcast8<8>(v, out);
+  } else {
+#pragma unroll
+    for (int u = 0; u < N; ++u) out[u] = __shfl(v, sub_base + k + u, 64);
+  }
+}
+
+template <int YT>
+__device__ __forceinline__ void store8(void* Y, size_t off, const float* y) {
+  if (YT == 1) {
+    *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(Y) + off) = f32x8_to_bf16(y);
+  } else if (YT == 2) {
+    f16x8 o;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) o[q] = (_Float16)y[q];
+    *reinterpret_cast<f16x8*>(reinterpret_cast<uint16_t*>(Y) + off) = o;
+  } else {
+    float4* p = reinterpret_cast<float4*>(reinterpret_cast<float*>(Y) + off);
+    p[0] = make_float4(y[0], y[1], y[2], y[3]);
+    p[1] = make_float4(y[4], y[5], y[6], y[7]);
+  }
+}
+
+// acc[q] = fmaf(w[u], X[j[u], f0 + q], acc[q]) for u = 0..N-1 in that order, the N rows
+// loaded before the first multiply-add
+template <int XT, int N>
+__device__ __forceinline__ void wgather_step(const void* __restrict__ X, const int* j, const int* w, int ldx,
+                                             int f0, float* acc) {
+  Raw8<XT> r[N];
+#pragma unroll
+  for (int u = 0; u < N; ++u) r[u] = load_raw8<XT>(X, (size_t)j[u] * ldx + f0);
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    float a[8];
+    raw8_to_f32<XT>(r[u], a);
+    const float wu = __int_as_float(w[u]);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) acc[q] = fmaf(wu, a[q], acc[q]);
+  }
+}
+
+}  // namespace
+
+// wcols: output columns this launch writes from its base (the row stride for a whole-row
+// launch, the slab width for a column-slab launch); columns [F, wcols) are written 0
+template <int L, int XT, int YT>
+__global__ __launch_bounds__(256) void wspmm_kernel(
+    const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ val,
+    const int* __restrict__ eperm, const void* __restrict__ X, void* __restrict__ Y,
+    const float* __restrict__ rscale, const float* __restrict__ cscale, const float* __restrict__ bias,
+    int n_rows, int F, int ldx, int ldy, int relu, int wcols) {
+  constexpr int RPW = 64 / L;
+  const int lane = threadIdx.x & 63;
+  const int sub = lane / L, sl = lane - sub * L, sub_base = sub * L;
+  const unsigned blk = xcd_remap(blockIdx.x, gridDim.x);
+  const int row = (blk * (blockDim.x >> 6) + (threadIdx.x >> 6)) * RPW + sub;
+  const bool rv = row < n_rows;
+  const int f0 = sl * 8;
+  const bool fv = rv && f0 < F;
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const int e0 = rv ? rowptr[row] : 0, e1 = rv ? rowptr[row + 1] : 0;
+  if (e1 > e0) {                                  // uniform per sub-group
+    // lane sl's edge of a chunk: its id and value, from an address clamped into the row
+    // (an unconditional load: a "load or 0" would branch and wait at the join)
+    auto edge = [&](int e, int& j, float& v) {
+      const int ec = min(e, e1 - 1);
+      j = col[ec];
+      v = val[eperm ? eperm[ec] : ec];
+    };
+    int nxj;
+    float nxv;
+    edge(e0 + sl, nxj, nxv);
+    for (int e = e0; e < e1; e += L) {
+      const int myj = nxj;
+      const float myv = nxv;
+      edge(e + L + sl, nxj, nxv);                 // the next chunk, under this chunk's gathers
+      // the edge's weight, rounded once: val * cscale
+      const int myw = __float_as_int(cscale ? myv * cscale[myj] : myv);
+      const int cnt = min(L, e1 - e);
+      int k = 0;
+      for (; k + 8 <= cnt; k += 8) {
+        int j[8], w[8];
+        sub_bcast<L, 8>(myj, sub_base, k, j);
+        sub_bcast<L, 8>(myw, sub_base, k, w);
+        if (fv) wgather_step<XT, 8>(X, j, w, ldx, f0, acc);
+      }
+      for (; k + 4 <= cnt; k += 4) {
+        int j[4], w[4];
+        sub_bcast<L, 4>(myj, sub_base, k, j);
+        sub_bcast<L, 4>(myw, sub_base, k, w);
+        if (fv) wgather_step<XT, 4>(X, j, w, ldx, f0, acc);
+      }
+      for (; k < cnt; ++k) {
+        int j[1], w[1];
+        sub_bcast<L, 1>(myj, sub_base, k, j);
+        sub_bcast<L, 1>(myw, sub_base, k, w);
+        if (fv) wgather_step<XT, 1>(X, j, w, ldx, f0, acc);
+      }
+    }
+  }
+  if (!rv || f0 >= wcols) return;
+  const float rs = rscale ? rscale[row] : 1.f;
+  float y[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const int f = f0 + q;
+    float v = acc[q] * rs + ((bias && f < F) ? bias[f] : 0.f);
+    if (relu) v = fmaxf(v, 0.f);
+    y[q] = f < F ? v : 0.f;
+  }
+  store8<YT>(Y, (size_t)row * ldy + f0, y);
+}
+
+// out[e] for the edges of row i.  Row i's slice of A stays in registers; each gathered row
+// of B gives 8 products per lane (one fmaf chain in feature order).  Eight edges at a
+// time: the 8 partial sums of a lane are combined with those of the lanes sl ^ 4, sl ^ 2,
+// sl ^ 1 in an exchange tree that halves the values a lane keeps at every level (4 + 2 + 1
+// exchanges instead of 8 x 3), then the remaining levels sl ^ 8 .. sl ^ L/2 add single
+// values: the dot product of edge k + (sl & 7) is in every lane, and the lane whose index
+// in the sub-group is that edge's index in the chunk keeps it.  A chunk of L results is
+// stored with ONE coalesced write, out[e + sl].
+// first / last: a width above 512 runs as launches over 512-column slabs in stream order;
+// a launch that is not the first adds to the sum its predecessor left in out[e], and the
+// last one applies the scales -- an ordered sum, never an unordered accumulation.
+template <int L, int T>
+__global__ __launch_bounds__(256) void sddmm_kernel(
+    const int* __restrict__ rowptr, const int* __restrict__ col, const void* __restrict__ A,
+    const void* __restrict__ B, float* __restrict__ out, const float* __restrict__ rscale,
+    const float* __restrict__ cscale, int n_rows, int F, int lda, int ldb, int first, int last) {
+  constexpr int RPW = 64 / L;
+  const int lane = threadIdx.x & 63;
+  const int sub = lane / L, sl = lane - sub * L, sub_base = sub * L;
+  const unsigned blk = xcd_remap(blockIdx.x, gridDim.x);
+  const int row = (blk * (blockDim.x >> 6) + (threadIdx.x >> 6)) * RPW + sub;
+  if (row >= n_rows) return;                      // uniform per sub-group
+  const int e0 = rowptr[row], e1 = rowptr[row + 1];
+  if (e1 <= e0) return;                           // uniform per sub-group
+  const int f0 = sl * 8;
+  const bool fv = f0 < F;
+  const int nq = F - f0;                          // this lane's valid features: min(8, nq)
+  float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (fv) {
+    raw8_to_f32<T>(load_raw8<T>(A, (size_t)row * lda + f0), a);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) a[q] = q < nq ? a[q] : 0.f;
+  }
+  const float rs = (last && rscale) ? rscale[row] : 1.f;
+  int nxj = col[min(e0 + sl, e1 - 1)];
+  for (int e = e0; e < e1; e += L) {
+    const int myj = nxj;
+    nxj = col[min(e + L + sl, e1 - 1)];
+    const int cnt = min(L, e1 - e);
+    const bool mine = sl < cnt;
+    // loaded beside the gathers, used at the store
+    const float mycs = (last && cscale && mine) ? cscale[myj] : 1.f;
+    const float prev = (!first && mine) ? out[e + sl] : 0.f;
+    float res = 0.f;
+    for (int k = 0; k < cnt; k += 8) {
+      int j[8];
+      sub_bcast<L, 8>(myj, sub_base, k, j);
+      float p[8];
+      if (fv) {
+        Raw8<T> r[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          if (k + u < cnt) r[u] = load_raw8<T>(B, (size_t)j[u] * ldb + f0);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          p[u] = 0.f;
+          if (k + u < cnt) {
+            float b[8];
+            raw8_to_f32<T>(r[u], b);
+            // (padding columns of B may hold anything: they are not multiplied)
+#pragma unroll
+            for (int q = 0; q < 8; ++q) p[u] = fmaf(a[q], q < nq ? b[q] : 0.f, p[u]);
+          }
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) p[u] = 0.f;
+      }
+      // exchange tree over the lanes sl ^ 4, sl ^ 2, sl ^ 1: edge (sl & 7) stays
+      const bool b4 = sl & 4, b2 = sl & 2, b1 = sl & 1;
+      float s4[4], s2[2];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float keep = b4 ? p[i + 4] : p[i], send = b4 ? p[i] : p[i + 4];
+        s4[i] = keep + __shfl_xor(send, 4, 64);
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const float keep = b2 ? s4[i + 2] : s4[i], send = b2 ? s4[i] : s4[i + 2];
+        s2[i] = keep + __shfl_xor(send, 2, 64);
+      }
+      float s = (b1 ? s2[1] : s2[0]) + __shfl_xor(b1 ? s2[0] : s2[1], 1, 64);
+#pragma unroll
+      for (int off = 8; off < L; off <<= 1) s += __shfl_xor(s, off, 64);
+      if ((sl >> 3) == (k >> 3)) res = s;
+    }
+    if (mine) {
+      const float v = prev + res;
+      out[e + sl] = last ? (rs * mycs) * v : v;
+    }
+  }
+}
+
+// ---------------------------------------------------------------- launchers
+template <int L>
+static int wspmm_dispatch(const int* rowptr, const int* col, const float* val, const int* eperm, const void* X,
+                          void* Y, const float* rs, const float* cs, const float* bias, int n_rows, int F, int ldx,
+                          int ldy, int xt, int yt, int relu, int wc, hipStream_t st) {
+  constexpr int RPB = 4 * (64 / L);               // rows per 256-thread block
+  dim3 grid((n_rows + RPB - 1) / RPB), block(256);
+#define CGNN_WSPMM(XT, YT)                                                                                  \
+  hipLaunchKernelGGL((wspmm_kernel<L, XT, YT>), grid, block, 0, st, rowptr, col, val, eperm, X, Y, rs, cs, \
+                     bias, n_rows, F, ldx, ldy, relu, wc)
+  // element-type codes: 0 fp32, 1 bf16, 2 fp16
+  if (xt == 1 && yt == 1) CGNN_WSPMM(1, 1);
+  else if (xt == 1 && yt == 0) CGNN_WSPMM(1, 0);
+  else if (xt == 2 && yt == 2) CGNN_WSPMM(2, 2);
+  else if (xt == 2 && yt == 0) CGNN_WSPMM(2, 0);
+  else if (xt == 0 && yt == 0) CGNN_WSPMM(0, 0);
+  else return -5;
+#undef CGNN_WSPMM
+  return (int)hipGetLastError();
+}
+
+static bool wspmm_pair_ok(int xt, int yt) {
+  return (xt == 1 && (yt == 1 || yt == 0)) || (xt == 2 && (yt == 2 || yt == 0)) || (xt == 0 && yt == 0);
+}
+
+// one launch writing output columns [0, wc) of its base (wc <= 512)
+static int wspmm_launch(const int* rowptr, const int* col, const float* val, const int* eperm, const void* X,
+                        void* Y, const float* rs, const float* cs, const float* bias, int n_rows, int F, int ldx,
+                        int ldy, int xt, int yt, int relu, int wc, hipStream_t st) {
+  const int w = std::max(F, wc);
+  if (w <= 64) return wspmm_dispatch<8>(rowptr, col, val, eperm, X, Y, rs, cs, bias, n_rows, F, ldx, ldy, xt, yt, relu, wc, st);
+  if (w <= 128) return wspmm_dispatch<16>(rowptr, col, val, eperm, X, Y, rs, cs, bias, n_rows, F, ldx, ldy, xt, yt, relu, wc, st);
+  if (w <= 256) return wspmm_dispatch<32>(rowptr, col, val, eperm, X, Y, rs, cs, bias, n_rows, F, ldx, ldy, xt, yt, relu, wc, st);
+  if (w <= 512) return wspmm_dispatch<64>(rowptr, col, val, eperm, X, Y, rs, cs, bias, n_rows, F, ldx, ldy, xt, yt, relu, wc, st);
+  return -1;
+}
+
+// No allocation and no synchronisation: capturable into a hipGraph.  Return codes: -3 a
+// row stride that is no multiple of 8 or narrower than F, -5 an (X, Y) type pair that is
+// not compiled, else the launch's HIP error.
+extern "C" int gnn_launch_wspmm(const int* rowptr, const int* col, const float* val, const int* eperm,
+                                const void* X, void* Y, const float* rscale, const float* cscale,
+                                const float* bias, int n_rows, int F, int ldx, int ldy, int xt, int yt, int relu,
+                                hipStream_t st) {
+  constexpr int slab = 512;
+  if (ldx <= 0 || ldy <= 0 || (ldx % 8) || (ldy % 8) || F < 0 || F > ldx || F > ldy) return -3;
+  if (!wspmm_pair_ok(xt, yt)) return -5;
+  if (n_rows <= 0) return 0;
+  if (ldy <= slab)
+    return wspmm_launch(rowptr, col, val, eperm, X, Y, rscale, cscale, bias, n_rows, F, ldx, ldy, xt, yt, relu, ldy,
+                        st);
+  // wide rows: column slabs of 512 output columns (16-byte aligned offsets), one launch
+  // each; the last slabs also write the padding columns up to ldy
+  const size_t xs = xt ? 2 : 4, ys = yt ? 2 : 4;
+  for (int c0 = 0; c0 < ldy; c0 += slab) {
+    const int fc = std::max(0, std::min(slab, F - c0));
+    const int wc = std::min(slab, ldy - c0);
+    const int rc = wspmm_launch(rowptr, col, val, eperm, (const char*)X + (fc ? c0 * xs : 0), (char*)Y + c0 * ys,
+                                rscale, cscale, bias && fc ? bias + c0 : nullptr, n_rows, fc, ldx, ldy, xt, yt,
+                                relu, wc, st);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+template <int L>
+static int sddmm_dispatch(const int* rowptr, const int* col, const void* A, const void* B, float* out,
+                          const float* rs, const float* cs, int n_rows, int F, int lda, int ldb, int t, int first,
+                          int last, hipStream_t st) {
+  constexpr int RPB = 4 * (64 / L);
+  dim3 grid((n_rows + RPB - 1) / RPB), block(256);
+#define CGNN_SDDMM(T)                                                                                         \
+  hipLaunchKernelGGL((sddmm_kernel<L, T>), grid, block, 0, st, rowptr, col, A, B, out, rs, cs, n_rows, F, lda, \
+                     ldb, first, last)
+  if (t == 0) CGNN_SDDMM(0);
+  else if (t == 1) CGNN_SDDMM(1);
+  else if (t == 2) CGNN_SDDMM(2);
+  else return -5;
+#undef CGNN_SDDMM
+  return (int)hipGetLastError();
+}
+
+// A and B share the storage type t.  Same return codes as gnn_launch_wspmm.
+extern "C" int gnn_launch_sddmm(const int* rowptr, const int* col, const void* A, const void* B, float* out,
+                                const float* rscale, const float* cscale, int n_rows, int F, int lda, int ldb,
+                                int t, hipStream_t st) {
+  constexpr int slab = 512;
+  if (lda <= 0 || ldb <= 0 || (lda % 8) || (ldb % 8) || F <= 0 || F > lda || F > ldb) return -3;
+  if (t < 0 || t > 2) return -5;
+  if (n_rows <= 0) return 0;
+  const size_t es = t ? 2 : 4;
+  for (int c0 = 0; c0 < F; c0 += slab) {
+    const int fc = std::min(slab, F - c0);
+    const void* a = (const char*)A + c0 * es;
+    const void* b = (const char*)B + c0 * es;
+    const int first = c0 == 0, last = c0 + slab >= F;
+    int rc;
+    if (fc <= 64) rc = sddmm_dispatch<8>(rowptr, col, a, b, out, rscale, cscale, n_rows, fc, lda, ldb, t, first, last, st);
+    else if (fc <= 128) rc = sddmm_dispatch<16>(rowptr, col, a, b, out, rscale, cscale, n_rows, fc, lda, ldb, t, first, last, st);
+    else if (fc <= 256) rc = sddmm_dispatch<32>(rowptr, col, a, b, out, rscale, cscale, n_rows, fc, lda, ldb, t, first, last, st);
+    else rc = sddmm_dispatch<64>(rowptr, col, a, b, out, rscale, cscale, n_rows, fc, lda, ldb, t, first, last, st);
+    if (rc) return rc;
+  }
+  return 0;
+}

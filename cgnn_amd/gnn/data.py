@@ -98,6 +98,49 @@ def build_csr(n: int, src: np.ndarray, dst: np.ndarray, device=None):
     return torch.from_numpy(np.asarray(rp).astype(np.int32)), torch.from_numpy(np.asarray(col))
 
 
+def _weighted_csr64(n: int, src, dst, weight, self_loops=None):
+    """``build_weighted_csr`` on the host with the summed weights still in fp64."""
+    s = torch.as_tensor(np.asarray(src)).to(torch.int64).flatten().cpu()
+    d = torch.as_tensor(np.asarray(dst)).to(torch.int64).flatten().cpu()
+    if weight is None:
+        w = torch.ones(s.numel(), dtype=torch.float64)
+    else:
+        w = torch.as_tensor(weight).detach().to(torch.float64).flatten().cpu()
+    if not (s.numel() == d.numel() == w.numel()):
+        raise ValueError("src, dst and weight must have one entry per edge")
+    if s.numel() and (int(min(s.min(), d.min())) < 0 or int(max(s.max(), d.max())) >= n):
+        raise ValueError("edge endpoints outside [0, %d)" % n)
+    # key = row * n + column: unique() sorts by destination, then by source
+    key, inv = torch.unique(d * n + s, return_inverse=True)
+    wsum = torch.zeros(key.numel(), dtype=torch.float64).index_add_(0, inv, w)
+    if self_loops is not None:
+        diag = torch.arange(n, dtype=torch.int64) * (n + 1)
+        add = diag[~torch.isin(diag, key)]            # a given self loop is kept as it is
+        key = torch.cat([key, add])
+        wsum = torch.cat([wsum, torch.full((add.numel(),), float(self_loops), dtype=torch.float64)])
+        order = torch.argsort(key)                    # (the keys are distinct)
+        key, wsum = key[order], wsum[order]
+    if key.numel() >= 2 ** 31:
+        raise ValueError("nnz >= 2^31 needs int64 CSR (graph must be sharded)")
+    r = key // n
+    rowptr = torch.zeros(n + 1, dtype=torch.int64)
+    rowptr[1:] = torch.cumsum(torch.bincount(r, minlength=n), 0)
+    return rowptr.to(torch.int32), (key - r * n).to(torch.int32), wsum
+
+
+def build_weighted_csr(n: int, src, dst, weight, device=None, self_loops=None):
+    """Directed, edge-weighted CSR of the given edges (row = destination, column = source;
+    nothing is symmetrised): duplicate edges are coalesced by summing their weights (in
+    fp64, rounded once), the edges of a row are sorted by source id.  ``self_loops=w0``
+    adds weight ``w0`` on the diagonal of every node that has no self loop of its own (a
+    given self loop is kept, as PyG's ``add_remaining_self_loops`` does).  Returns
+    ``(rowptr int32 [n + 1], col int32 [nnz], val fp32 [nnz])`` on ``device``.  Setup
+    code: host sorts."""
+    rowptr, col, w = _weighted_csr64(n, src, dst, weight, self_loops)
+    device = torch.device(device) if device is not None else torch.device("cpu")
+    return rowptr.to(device), col.to(device), w.float().to(device)
+
+
 ID_ORDERS = {"banded": 0, "shuffled": 1}
 
 

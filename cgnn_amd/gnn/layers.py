@@ -10,6 +10,9 @@ track, not in the reference.
   gathered rows are the narrower of the two widths) with the normalisation,
   bias and ReLU inside the SpMM and a split-K weight gradient.
 * ``GCN`` -- L layers with ReLU + dropout between them.
+* ``WeightedGraph`` / ``weighted_aggregate`` -- the same layers over a directed graph
+  with one value per edge (``ops.wspmm``): the backward runs over the transposed CSR,
+  and the edge values receive a gradient (``ops.sddmm``) when they require one.
 
 Everything runs on the same ``ops.spmm`` as the fused 2-layer trainer (HIP on
 GPU tensors, PyTorch index ops on CPU tensors); dense products are hipBLASLt
@@ -107,7 +110,154 @@ class _GCNLayer(torch.autograd.Function):
         return dh, dW, db, None, None
 
 
-def gcn_layer(h: torch.Tensor, W: torch.Tensor, b: torch.Tensor, g: NormGraph, relu: bool) -> torch.Tensor:
+class WeightedGraph:
+    """Directed CSR with one fp32 value per edge (row = destination, column = source) and
+    optional row / column scales: ``Â[i, j] = rscale[i] * val[e] * cscale[j]`` for the edge
+    e = (i, j).  ``n_src`` (default: the number of rows) is the number of source nodes of a
+    rectangular graph."""
+
+    def __init__(self, rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, n_src: Optional[int] = None,
+                 rscale: Optional[torch.Tensor] = None, cscale: Optional[torch.Tensor] = None):
+        self.rowptr, self.col, self.val = rowptr.contiguous(), col.contiguous(), val.contiguous()
+        self.n = rowptr.numel() - 1
+        self.n_src = self.n if n_src is None else int(n_src)
+        self.rscale = rscale.contiguous() if rscale is not None else None
+        self.cscale = cscale.contiguous() if cscale is not None else None
+        if self.val.numel() != self.col.numel():
+            raise ValueError("WeightedGraph: %d values for %d edges" % (self.val.numel(), self.col.numel()))
+        self._t = None
+
+    def transposed(self):
+        """``(rowptr_t, col_t, eperm)``: the CSR of the transpose and, per transposed edge,
+        the index of its forward edge (so the backward reads ``val`` in place).  Built once."""
+        if self._t is None:
+            from .sage import transpose_csr
+            self._t = transpose_csr(self.rowptr, self.col, self.n_src, with_perm=True)
+        return self._t
+
+    @classmethod
+    def from_edges(cls, n: int, src, dst, weight=None, self_loops: Optional[float] = 1.0,
+                   normalize: Optional[str] = "sym", device=None) -> "WeightedGraph":
+        """Graph of the directed edges src -> dst (``data.build_weighted_csr``: duplicates
+        summed, self loops of weight ``self_loops`` added where missing).  ``normalize``:
+        ``"sym"``: val_ij = w_ij / sqrt(d_i d_j); ``"rw"``: val_ij = w_ij / d_i; ``None``:
+        the weights as they are -- d_i the sum of the weights of row i after self loops; a
+        row with d_i = 0 gets scale 0.  The normalised values are computed in fp64 and
+        rounded once to fp32."""
+        from .data import _weighted_csr64
+        rowptr, col, w = _weighted_csr64(n, src, dst, weight, self_loops)
+        if normalize is not None:
+            rows = ops._row_ids(rowptr)
+            d = torch.zeros(n, dtype=torch.float64).index_add_(0, rows, w)
+            pos = d > 0
+            if normalize == "sym":
+                ok = pos[rows] & pos[col.long()]
+                dd = torch.where(ok, d[rows] * d[col.long()], torch.ones_like(w))
+                w = torch.where(ok, w / dd.sqrt(), torch.zeros_like(w))
+            elif normalize == "rw":
+                w = torch.where(pos[rows], w / torch.where(pos, d, torch.ones_like(d))[rows], torch.zeros_like(w))
+            else:
+                raise ValueError("normalize must be 'sym', 'rw' or None, got %r" % (normalize,))
+        device = torch.device(device) if device is not None else torch.device("cpu")
+        return cls(rowptr.to(device), col.to(device), w.float().to(device))
+
+    @classmethod
+    def from_norm(cls, g: NormGraph) -> "WeightedGraph":
+        """The normalised adjacency of a :class:`NormGraph` in factored form: unit values,
+        ``rscale = cscale = dinv``."""
+        return cls(g.rowptr, g.col, torch.ones(g.col.numel(), dtype=torch.float32, device=g.col.device),
+                   rscale=g.dinv, cscale=g.dinv)
+
+
+def _wspmm_fwd(x, g: WeightedGraph, val, bias=None, relu=False):
+    """act(Â x + bias) in the storage dtype of x (columns padded to a multiple of 8)."""
+    F = x.shape[1]
+    xs = pad_cols(x).contiguous()
+    out = ops.wspmm(g.rowptr, g.col, val, xs, F, rscale=g.rscale, cscale=g.cscale, bias=bias, relu=relu,
+                    out_dtype=x.dtype, ld_out=xs.shape[1])
+    return out[:, :F] if out.shape[1] != F else out
+
+
+def _wspmm_bwd(dy, g: WeightedGraph, val):
+    """Âᵀ dy: the aggregate over the transposed CSR, the forward's values read through the
+    edge permutation, the roles of the row and column scale swapped."""
+    rp_t, col_t, eperm = g.transposed()
+    F = dy.shape[1]
+    dyp = pad_cols(dy).contiguous()
+    out = ops.wspmm(rp_t, col_t, val, dyp, F, rscale=g.cscale, cscale=g.rscale, eperm=eperm, out_dtype=dy.dtype,
+                    ld_out=dyp.shape[1])
+    return out[:, :F] if out.shape[1] != F else out
+
+
+def _edge_grad(dy, x, g: WeightedGraph, val):
+    """d loss / d val[e] = rscale[i] cscale[j] <dy[i], x[j]> for e = (i, j)."""
+    F = dy.shape[1]
+    d = ops.sddmm(g.rowptr, g.col, pad_cols(dy).contiguous(), pad_cols(x).contiguous(), F, rscale=g.rscale,
+                  cscale=g.cscale)
+    return d.to(val.dtype)
+
+
+class _WeightedAggregate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, val, g: WeightedGraph):
+        ctx.g = g
+        ctx.save_for_backward(x, val)
+        return _wspmm_fwd(x, g, val.detach())
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, val = ctx.saved_tensors
+        gy = gy.contiguous()
+        dx = _wspmm_bwd(gy, ctx.g, val) if ctx.needs_input_grad[0] else None
+        dval = _edge_grad(gy, x, ctx.g, val) if ctx.needs_input_grad[1] else None
+        return dx, dval, None
+
+
+def weighted_aggregate(x: torch.Tensor, g: WeightedGraph, val: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``Â x`` over an edge-weighted, possibly directed graph.  ``val`` (default ``g.val``):
+    the edge values; a tensor that requires grad receives d loss / d val (fp32), which is how
+    edge weights are learned or explained."""
+    return _WeightedAggregate.apply(x, g.val if val is None else val, g)
+
+
+class _WeightedGCNLayer(torch.autograd.Function):
+    """``act(Â (H W) + b)`` on a :class:`WeightedGraph`: bias and ReLU in the weighted
+    SpMM's epilogue.  Backward: ReLU mask, ``db = sum dY``, ``dZ = Âᵀ dY`` (transposed
+    pass), ``dW = H^T dZ`` (``ops.tall_gemm_tn``), ``dH = dZ W^T`` and, when asked for,
+    ``d val[e] = rscale_i cscale_j <dY_i, (H W)_j>`` (``ops.sddmm``)."""
+
+    @staticmethod
+    def forward(ctx, h, W, b, val, g: WeightedGraph, relu: bool):
+        Wc = W.to(h.dtype)
+        z = h @ Wc
+        y = _wspmm_fwd(z, g, val.detach(), bias=b.float().contiguous(), relu=relu)
+        ctx.g, ctx.relu = g, relu
+        ctx.save_for_backward(h, Wc, val, y if relu else None, z if ctx.needs_input_grad[3] else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        h, Wc, val, y, z = ctx.saved_tensors
+        g = ctx.g
+        dy = dy.contiguous()
+        if ctx.relu:
+            dy = torch.ops.aten.threshold_backward(dy, y, 0)
+        db = dy.float().sum(0)
+        dz = _wspmm_bwd(dy, g, val)
+        dW = ops.tall_gemm_tn(h, dz)
+        dh = dz @ Wc.t() if ctx.needs_input_grad[0] else None
+        dval = _edge_grad(dy, z, g, val) if ctx.needs_input_grad[3] else None
+        return dh, dW, db, dval, None, None
+
+
+def gcn_layer(h: torch.Tensor, W: torch.Tensor, b: torch.Tensor, g, relu: bool,
+              edge_weight: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``act(Â (H W) + b)``; ``g`` a :class:`NormGraph`, or a :class:`WeightedGraph` with
+    optional ``edge_weight`` (default ``g.val``) in place of its values."""
+    if isinstance(g, WeightedGraph):
+        return _WeightedGCNLayer.apply(h, W, b, g.val if edge_weight is None else edge_weight, g, relu)
+    if edge_weight is not None:
+        raise TypeError("edge_weight needs a WeightedGraph (WeightedGraph.from_norm(g))")
     return _GCNLayer.apply(h, W, b, g, relu)
 
 
@@ -120,8 +270,8 @@ class GCNConv(torch.nn.Module):
         self.weight = torch.nn.Parameter((torch.rand(in_dim, out_dim, generator=generator) * 2 - 1) * bound)
         self.bias = torch.nn.Parameter(torch.zeros(out_dim))
 
-    def forward(self, h: torch.Tensor, g: NormGraph, relu: bool = False) -> torch.Tensor:
-        return gcn_layer(h, self.weight, self.bias, g, relu)
+    def forward(self, h: torch.Tensor, g, relu: bool = False, edge_weight: Optional[torch.Tensor] = None):
+        return gcn_layer(h, self.weight, self.bias, g, relu, edge_weight)
 
 
 class GCN(torch.nn.Module):
@@ -134,11 +284,11 @@ class GCN(torch.nn.Module):
         self.convs = torch.nn.ModuleList(GCNConv(a, b, gen) for a, b in zip(dims[:-1], dims[1:]))
         self.dropout = float(dropout)
 
-    def forward(self, x: torch.Tensor, g: NormGraph) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, g, edge_weight: Optional[torch.Tensor] = None) -> torch.Tensor:
         h = x
         L = len(self.convs)
         for k, conv in enumerate(self.convs):
-            h = conv(h, g, relu=k < L - 1)
+            h = conv(h, g, relu=k < L - 1, edge_weight=edge_weight)
             if k < L - 1 and self.training and self.dropout > 0:
                 h = torch.nn.functional.dropout(h, self.dropout)
         return h

@@ -1,8 +1,9 @@
 """GNN-track device ops (HIP on GPU tensors, PyTorch reference on CPU tensors).
 
 The CPU branch is the numerical reference used by the tests (and lets the
-models run in CI); on a GPU the HIP kernels of csrc/kernels/gnn_sparse.hip are
-mandatory -- a missing extension raises instead of silently falling back.
+models run in CI); on a GPU the HIP kernels of csrc/kernels/gnn_sparse.hip (and
+gnn_wspmm.hip for the edge-weighted ops) are mandatory -- a missing extension raises
+instead of silently falling back.
 """
 from __future__ import annotations
 
@@ -106,6 +107,110 @@ def spmm(rowptr, col, X, F, rscale=None, bias=None, relu=False, out=None, out_dt
     out[:n, :F] = acc.to(out.dtype)
     if unit_col >= 0:
         out[:n, unit_col] = 1
+    return out
+
+
+def _acc_dtype(dt):
+    return torch.float64 if dt == torch.float64 else torch.float32
+
+
+def wspmm(rowptr, col, val, X, F, rscale=None, cscale=None, bias=None, relu=False, eperm=None, out=None,
+          out_dtype=None, ld_out=None):
+    """Y[i,:F] = act(rscale[i] * sum_{e in row i} val[p(e)] * cscale[col[e]] * X[col[e],:F] + bias):
+    the CSR aggregate with one caller-supplied value per edge (gnn_wspmm.hip, wspmm_kernel).
+    ``val`` is fp32 (GPU); ``p(e) = eperm[e]`` with an edge permutation (int32 [nnz], e.g.
+    the transposed CSR's map to the forward edges, so the forward's value array is read in
+    place), else ``e``.  Padding columns of Y are written 0.  The GPU compiles the (X, Y)
+    pairs (bf16, bf16), (bf16, fp32), (fp16, fp16), (fp16, fp32), (fp32, fp32); ``out_dtype``
+    defaults to X's.  Per row the multiply-adds run in edge order whatever the launch: the
+    output is bit-identical from run to run.  CPU tensors: PyTorch, fp32 accumulation
+    (fp64 for fp64 inputs)."""
+    n = rowptr.numel() - 1
+    nnz = col.numel()
+    ldo = ld_out or X.shape[1]
+    if out is None:
+        out = torch.empty(n, ldo, dtype=out_dtype or X.dtype, device=X.device)
+    if checks.enabled():
+        checks.csr(rowptr, col, X.shape[0], "wspmm")
+        checks.rows(out, n, "wspmm out")
+        checks.rows(rscale, n, "wspmm rscale")
+        checks.rows(cscale, X.shape[0], "wspmm cscale")
+        if eperm is None:
+            if val.numel() < nnz:
+                raise ValueError("CGNN_CHECK: wspmm: %d values for %d edges" % (val.numel(), nnz))
+        else:
+            if eperm.numel() != nnz:
+                raise ValueError("CGNN_CHECK: wspmm: eperm has %d entries for %d edges" % (eperm.numel(), nnz))
+            checks.index(eperm, val.numel(), "wspmm eperm")
+    if X.is_cuda:
+        if val.dtype != torch.float32:
+            raise TypeError("wspmm: edge values must be fp32 on the GPU, got %s" % val.dtype)
+        if eperm is not None and eperm.dtype != torch.int32:
+            raise TypeError("wspmm: eperm must be int32")
+        if not (X.is_contiguous() and out.is_contiguous() and val.is_contiguous()):
+            raise ValueError("wspmm: contiguous operands expected")
+        native.hip().gnn_wspmm(rowptr.data_ptr(), col.data_ptr(), val.data_ptr(),
+                               eperm.data_ptr() if eperm is not None else 0, X.data_ptr(), out.data_ptr(),
+                               rscale.data_ptr() if rscale is not None else 0,
+                               cscale.data_ptr() if cscale is not None else 0,
+                               bias.data_ptr() if bias is not None else 0, n, F, X.shape[1], out.shape[1],
+                               dtype_code(X.dtype), dtype_code(out.dtype), int(relu), _st(X))
+        return out
+    at = _acc_dtype(X.dtype)
+    rows = _row_ids(rowptr)
+    j = col.long()
+    w = (val[eperm.long()] if eperm is not None else val[:nnz]).to(at)
+    if cscale is not None:
+        w = w * cscale[j].to(at)
+    acc = torch.zeros(n, F, dtype=at).index_add_(0, rows, X[j, :F].to(at) * w[:, None])
+    if rscale is not None:
+        acc = acc * rscale[:n, None].to(at)
+    if bias is not None:
+        acc = acc + bias[:F].to(at)
+    if relu:
+        acc = acc.clamp_min(0)
+    out[:n].zero_()
+    out[:n, :F] = acc.to(out.dtype)
+    return out
+
+
+def sddmm(rowptr, col, A, B, F, rscale=None, cscale=None, out=None):
+    """out[e] = rscale[i] * cscale[j] * sum_{f<F} A[i,f] B[j,f] for every edge e = (i, j =
+    col[e]) of the CSR -- the gradient of ``wspmm`` with respect to each edge value
+    (gnn_wspmm.hip, sddmm_kernel).  A [n_rows, lda] and B [n_src, ldb] share one storage
+    type (fp32 / bf16 / fp16); ``out`` is fp32 [nnz] (fp64 for fp64 inputs on the CPU).
+    Fixed-order sums, no atomics: bit-identical from run to run."""
+    n = rowptr.numel() - 1
+    nnz = col.numel()
+    if A.dtype != B.dtype:
+        raise TypeError("sddmm: A and B must share a dtype, got %s and %s" % (A.dtype, B.dtype))
+    if out is None:
+        out = torch.empty(nnz, dtype=_acc_dtype(A.dtype), device=A.device)
+    if checks.enabled():
+        checks.csr(rowptr, col, B.shape[0], "sddmm")
+        checks.rows(A, n, "sddmm A")
+        checks.rows(out, nnz, "sddmm out")
+        checks.rows(rscale, n, "sddmm rscale")
+        checks.rows(cscale, B.shape[0], "sddmm cscale")
+    if A.is_cuda:
+        if out.dtype != torch.float32:
+            raise TypeError("sddmm: the output is fp32, got %s" % out.dtype)
+        if not (A.is_contiguous() and B.is_contiguous() and out.is_contiguous()):
+            raise ValueError("sddmm: contiguous operands expected")
+        native.hip().gnn_sddmm(rowptr.data_ptr(), col.data_ptr(), A.data_ptr(), B.data_ptr(), out.data_ptr(),
+                               rscale.data_ptr() if rscale is not None else 0,
+                               cscale.data_ptr() if cscale is not None else 0, n, F, A.shape[1], B.shape[1],
+                               dtype_code(A.dtype), _st(A))
+        return out
+    at = _acc_dtype(A.dtype)
+    rows = _row_ids(rowptr)
+    j = col.long()
+    d = (A[rows, :F].to(at) * B[j, :F].to(at)).sum(1)
+    if rscale is not None:
+        d = d * rscale[rows].to(at)
+    if cscale is not None:
+        d = d * cscale[j].to(at)
+    out[:nnz] = d.to(out.dtype)
     return out
 
 
