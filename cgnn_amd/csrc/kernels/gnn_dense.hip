@@ -114,7 +114,8 @@ __device__ __forceinline__ bf16x8 tr_frag(const uint16_t* base, int off0, int of
 // The next tile's AX rows are loaded right after the last hidden block's layer-1 MFMAs
 // (the registers of the current rows are dead from there), so the loads fly during
 // that block's epilogue, its layer-2 products and the Z2 stores.
-template <int KS, int HD, int DROP>
+// HOIST_OK: the launcher's promise that F > 16 (KS - 1), which the hoisted loads need (below).
+template <int KS, int HD, int DROP, bool HOIST_OK = true>
 __global__ __launch_bounds__(WAVES * 64) void gcn_dense_fwd_kernel(
     const uint16_t* __restrict__ AX, const float* __restrict__ W1, const float* __restrict__ b1,
     const float* __restrict__ W2, const float* __restrict__ dinv, uint16_t* __restrict__ H1,
@@ -161,8 +162,12 @@ __global__ __launch_bounds__(WAVES * 64) void gcn_dense_fwd_kernel(
   // rows (k >= F).
   // The hoisted next-tile loads fit the 128-register budget of 4 waves / SIMD only in
   // the bit-mode (p = 1/2) form up to 112 features: the other forms load each tile at
-  // its start (and keep the per-lane "load or zero" form, which needs fewer registers)
-  constexpr bool HOIST = DROP == 2 && KS <= 7;
+  // its start (and keep the per-lane "load or zero" form, which needs fewer registers).
+  // So does a shape that runs on a wider template than it needs (F <= 16 (KS - 1),
+  // HOIST_OK false): its row pitch may end before k-step KS - 2 does, and the unguarded
+  // loads would then read the next row -- past the buffer on the last row, where a NaN
+  // or Inf bit pattern meets a zero weight, becomes NaN and wipes the row.
+  constexpr bool HOIST = HOIST_OK && DROP == 2 && KS <= 7;
   bf16x8 bx[KS];
   // the row's D^-1/2 is loaded with its rows: loaded at the Z2 stores it was the newest
   // load, and waiting for it meant waiting for the next tile's rows (the prefetch) too
@@ -682,15 +687,15 @@ static int dense_grid(int n) {
   return std::max(1, std::min(cus, (tiles + WAVES - 1) / WAVES));
 }
 
-template <int KS, int HD, int DROP>
+template <int KS, int HD, int DROP, bool HOIST_OK = true>
 static int fwd_launch_d(const uint16_t* AX, const float* W1, const float* b1, const float* W2,
                         const float* dinv, uint16_t* H1, uint16_t* Z2, int n, int F, int ldx, int C,
                         int ldc, float p, uint32_t k0, uint32_t k1, uint32_t step, uint32_t thr8,
                         uint32_t row0, const int* stepp, uint16_t* kimg, hipStream_t st) {
   const size_t lds = sizeof(uint16_t) * ((size_t)HD * (KS * 16 + 8) + 64 * (size_t)(HD + 4)) + sizeof(float) * HD;
-  (void)hipFuncSetAttribute((const void*)gcn_dense_fwd_kernel<KS, HD, DROP>,
+  (void)hipFuncSetAttribute((const void*)gcn_dense_fwd_kernel<KS, HD, DROP, HOIST_OK>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((gcn_dense_fwd_kernel<KS, HD, DROP>), dim3(dense_grid(n)), dim3(WAVES * 64), lds, st, AX, W1,
+  hipLaunchKernelGGL((gcn_dense_fwd_kernel<KS, HD, DROP, HOIST_OK>), dim3(dense_grid(n)), dim3(WAVES * 64), lds, st, AX, W1,
                      b1, W2, dinv, H1, Z2, n, F, ldx, C, ldc, p, k0, k1, step, thr8, row0, stepp, kimg);
   if (DROP == 1 && kimg) {
     const long lanes = (long)((n + TILE - 1) / TILE) * 64;
@@ -705,9 +710,16 @@ static int fwd_launch(const uint16_t* AX, const float* W1, const float* b1, cons
                       const float* dinv, uint16_t* H1, uint16_t* Z2, int n, int F, int ldx, int C,
                       int ldc, float p, uint32_t k0, uint32_t k1, uint32_t step, uint32_t thr8,
                       uint32_t row0, const int* stepp, uint16_t* kimg, hipStream_t st) {
-  if (thr8 == 128)
+  if (thr8 == 128) {
+    // the hoisted row loads only where the shape fills its template (F > 16 (KS - 1)):
+    // the KS <= ks dispatch also brings narrower shapes here
+    if constexpr (KS <= 7)
+      if (F <= 16 * (KS - 1))
+        return fwd_launch_d<KS, HD, 2, false>(AX, W1, b1, W2, dinv, H1, Z2, n, F, ldx, C, ldc, p, k0, k1, step, thr8,
+                                              row0, stepp, kimg, st);
     return fwd_launch_d<KS, HD, 2>(AX, W1, b1, W2, dinv, H1, Z2, n, F, ldx, C, ldc, p, k0, k1, step, thr8, row0,
                                    stepp, kimg, st);
+  }
   if (thr8 > 0)
     return fwd_launch_d<KS, HD, 1>(AX, W1, b1, W2, dinv, H1, Z2, n, F, ldx, C, ldc, p, k0, k1, step, thr8, row0,
                                    stepp, kimg, st);
