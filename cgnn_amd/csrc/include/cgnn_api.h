@@ -1,0 +1,224 @@
+// The C ABI of the kernel library: every extern "C" launcher and query function of
+// csrc/kernels/*.hip, declared exactly once.  Each .hip file and bindings.cpp include
+// this header, so a definition that drifts from its declaration is a conflicting-types
+// compile error, never a silent argument mismatch at link time (extern "C" symbols
+// link by name alone).  Plain C++: bindings.cpp is not compiled as HIP.
+// tests/test_native_abi_cpu.py checks that no definition escapes the header.
+//
+// Conventions.  Device pointers are raw; the library never allocates device memory.
+// `st` is the stream every launch goes to.  An int-returning launcher returns
+//    0   launched
+//   >0   the hipError_t of the launch (hipGetLastError)
+//   -1   no compiled variant covers the shape (template width, tile, head count)
+//   -2   a size the kernels cannot serve: a row range or seed count out of bounds, LDS
+//        need over the limit, a missing scratch buffer (cgnn_*, rff_*, gnn_sw_*)
+//   -3   bad shape: a row stride that is no multiple of 8 or narrower than the row, a
+//        width or class count over the kernel's limit, a required pointer missing
+//   -4   the launch grid or the per-block row-id table would overflow
+//   -5   an element-type pair (X, Y storage type) that is not compiled
+// The *_supported / *_variant queries return 1 / 0 (or a variant number), the *_blocks,
+// *_tiles, *_chunks, *_width, *_slots, *_waves queries a count, *_bytes / *_halfwords /
+// *_floats / *_scratch / *_lds a buffer size; none of them launches anything.
+// The argument semantics are documented beside each definition.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+extern "C" {
+
+// ---- cgnn_kernels.hip: vector MMD, generator forward / backward, Adam, init
+int cgnn_mmd_supported_d(int D);
+int cgnn_mmd_mirror_slots(int D, int N);
+int cgnn_launch_mmd_rows(int mode, int D, const float* xhat, const float* data, float* gpart, float* lpart, int N,
+                         int R, int row_tiles, int n_chunks, int tpc, float gscale, int row_begin, int n_rows,
+                         hipStream_t st, int mirror);
+// all N rows (the engine's call)
+int cgnn_launch_mmd(int mode, int D, const float* xhat, const float* data, float* gpart, float* lpart, int N, int R,
+                    int row_tiles, int n_chunks, int tpc, float gscale, hipStream_t st, int mirror);
+int cgnn_launch_loss_finalize(const float* lpart, int n_parts, float* tt, float* last, float* acc, float inv_n2,
+                              int flags, float* hist, int hist_stride, const int* step_base, int step_off, int R,
+                              hipStream_t st);
+int cgnn_gen_supported_h(int H);
+size_t cgnn_gen_fwd_lds(int D, int prog_stride);
+int cgnn_launch_gen_fwd(const int* prog, int prog_stride, const float* params, int P, const float* data, float* xhat,
+                        float* noise, int NS, float* xnorm, const uint32_t* keys, const int* step_base, int step_off,
+                        int N, int D, int H, int R, hipStream_t st, int row0);
+int cgnn_gen_bwd_blocks(int N);
+size_t cgnn_gen_bwd_lds(int H, int max_in, int D, int prog_stride);
+// 1 the per-sample kernels, 2 the level-scheduled ones (cgnn_staged.hip), 0 neither fits
+int cgnn_gen_bwd_variant(int H, int max_in, int Dt, int prog_stride);
+int cgnn_gen_staged_supported(int H, int max_in, int Dt);
+int cgnn_launch_gen_bwd(const int* prog, int prog_stride, const float* params, int P, const float* xhat,
+                        const float* noise, int NS, const float* gradp, int n_chunks, int R, int N, int D, int Dt,
+                        int H, int max_in, float* gpart, hipStream_t st);
+int cgnn_launch_adam(float* params, float* m, float* v, const float* gpart, int G, const int* prog, int prog_stride,
+                     int P, const int* step_base, int step_off, float lr, float b1, float b2, float eps, int R,
+                     hipStream_t st);
+int cgnn_launch_init(float* params, float* m, float* v, const int* prog, int prog_stride, int P, const uint32_t* keys,
+                     float init_std, int R, hipStream_t st);
+int cgnn_launch_advance(int* step_base, int d_rng, int d_opt, hipStream_t st);
+
+// ---- cgnn_staged.hip: level-scheduled generator kernels (wide graphs)
+// out = {fwd_xg, bwd_xg, bwd_dg, W_fwd, W_bwd}; 0, or -1 when nothing fits
+int cgnn_staged_plan(int Dt, int H, int max_in, int W, int extra, int* out);
+int cgnn_staged_tiles(int N);
+int cgnn_launch_gen_noise(const int* prog, int ps, const uint32_t* keys, const int* step_base, int step_off,
+                          float* noise, int NS, int N, int D, int Dt, int R, int row0, hipStream_t st);
+// the forward that draws its own noise (keys != nullptr); only the engine calls it
+int cgnn_launch_gen_fwd_staged_draw(const int* prog, int ps, const int* sched, int ss, const float* params, int P,
+                                    const float* data, float* xhat, float* noise, int NS, float* xnorm, int N, int D,
+                                    int Dt, int H, int max_in, int R, int W, hipStream_t st, int force,
+                                    const uint32_t* keys, const int* step_base, int step_off, int row0);
+int cgnn_launch_gen_fwd_staged(const int* prog, int ps, const int* sched, int ss, const float* params, int P,
+                               const float* data, float* xhat, const float* noise, int NS, float* xnorm, int N, int D,
+                               int Dt, int H, int max_in, int R, int W, hipStream_t st, int force);
+int cgnn_launch_gen_bwd_staged(const int* prog, int ps, const int* sched, int ss, const float* params, int P,
+                               const float* xhat, const float* noise, int NS, const float* gradp, int n_chunks, int R,
+                               int N, int D, int Dt, int H, int max_in, int W, float* gpart, float* dxs,
+                               hipStream_t st, int force);
+
+// ---- mmd_mfma.hip: matrix-core MMD
+int cgnn_mmd_mfma_supported(int D);
+int cgnn_mmd_mfma_row_blocks(int N);
+int cgnn_launch_mmd_mfma_rows(int mode, int D, const float* xhat, const float* data, const float* xnorm,
+                              const float* ynorm, float* gpart, float* lpart, int N, int R, int n_chunks, int tpc,
+                              float gscale, int row_begin, int n_rows, hipStream_t st, int wide);
+// all N rows, automatic kernel choice (the engine's call)
+int cgnn_launch_mmd_mfma(int mode, int D, const float* xhat, const float* data, const float* xnorm,
+                         const float* ynorm, float* gpart, float* lpart, int N, int R, int n_chunks, int tpc,
+                         float gscale, hipStream_t st);
+
+// ---- rff_kernels.hip: Fourier (random-feature) MMD
+long rff_wide_scratch_floats(int N, int F, int R);
+int rff_launch_freqs(float* W, const uint32_t* keys, const int* step_base, int step_off, int k, int D, int n_gamma,
+                     int d_true, int R, hipStream_t st);
+int rff_launch_fwd_bwd(int mode, const float* xhat, const float* data, const float* W, float* diff, float* loss_part,
+                       float* grad, int N, int D, int F, int R, int k, float norm, hipStream_t st, int force_valu,
+                       float* scratch, int force_wide);
+
+// ---- cgnn_engine.hip: the native step engine; the handle is a cgnn::Engine*.  icfg /
+// fcfg / ptrs are positional (EngineConfig and Engine in that file name every slot).
+// These throw std::runtime_error instead of returning a code.
+void* cgnn_engine_create(const int* icfg, const float* fcfg, const void* const* ptrs, hipStream_t st);
+void cgnn_engine_destroy(void* e);
+int cgnn_engine_gen_blocks(void* e);
+int cgnn_engine_n_parts(void* e);
+void cgnn_engine_init(void* e);
+void cgnn_engine_tt(void* e);
+void cgnn_engine_run(void* e, int kind, int steps, int chunk, int hist);
+
+// ---- gnn_sparse.hip: SpMM family, fused SpMM + cross-entropy, elementwise, Adam
+int gnn_launch_spmm(const int* rowptr, const int* col, const void* X, void* Y, const float* rscale, const float* bias,
+                    int n_rows, int F, int ldx, int ldy, int xbf, int ybf, int relu, int unit_col, const float* init,
+                    int ldi, const float* cscale, int init_rows, int short_rows, hipStream_t st);
+int gnn_slab_sum(const float* P, long S, int W, float* stage, int G, float* out, const int* map, int* bump,
+                 hipStream_t st);
+int gnn_spmm_ce_blocks(int n_rows, int n_long);
+int gnn_launch_bias_relu_dropout(void* H, const float* bias, long rows, int F, int ld, float p, uint32_t k0,
+                                 uint32_t k1, uint32_t step, uint32_t row0, hipStream_t st);
+int gnn_launch_relu_dropout_bwd(void* dH, const void* H, long n, float p, hipStream_t st);
+int gnn_launch_spmm_ce(const int* rowptr, const int* col, const void* Z, const float* rscale, const float* bias,
+                       const int* labels, const uint8_t* mask, float* stats, void* G, const float* init, int ldi,
+                       int n_rows, int C, int ld, int mode, float inv_count, const int* gslot, int n_long,
+                       hipStream_t st);
+int gnn_launch_ell_build(const int* rowptr, const int* col, int* ell, int n_rows, hipStream_t st);
+int gnn_launch_spmm_ell(const int* ell, const int* col, const void* X, void* Y, const float* rscale, int n_rows,
+                        int F, int ldx, int ldy, long n_x_rows, const int* long_rows, int n_long, hipStream_t st);
+int gnn_launch_spmm_fan(const int* rowptr, const int* col, const void* X, void* Y, const float* rscale, int n_rows,
+                        int F, int ldx, int ldy, long n_x_rows, long nnz, int max_deg, hipStream_t st);
+int gnn_launch_adam(float* p, float* m, float* v, const float* g, int n, float lr, float b1, float b2, float eps,
+                    float wd, int* step, unsigned* done, int step_done, hipStream_t st);
+int gnn_launch_cast_bf16(const float* src, void* dst, long n, hipStream_t st);
+
+// ---- gnn_wspmm.hip: edge-weighted aggregate and its edge-value gradient.  xt / yt / t:
+// storage types; -3 for a bad stride, -5 for a type pair that is not compiled
+int gnn_launch_wspmm(const int* rowptr, const int* col, const float* val, const int* eperm, const void* X, void* Y,
+                     const float* rscale, const float* cscale, const float* bias, int n_rows, int F, int ldx, int ldy,
+                     int xt, int yt, int relu, hipStream_t st);
+int gnn_launch_sddmm(const int* rowptr, const int* col, const void* A, const void* B, float* out, const float* rscale,
+                     const float* cscale, int n_rows, int F, int lda, int ldb, int t, hipStream_t st);
+
+// ---- gnn_dense.hip: the fused two-layer dense GCN kernels.  The launchers return -1
+// when no compiled variant covers (F, HD, C); Python then raises
+int gnn_launch_dense_fwd(const void* AX, const float* W1, const float* b1, const float* W2, const float* dinv,
+                         void* H1, void* Z2, int n, int F, int ldx, int HD, int C, int ldc, float p, uint32_t k0,
+                         uint32_t k1, uint32_t step, uint32_t row0, const int* stepp, void* kimg, hipStream_t st);
+long gnn_keep_image_halfwords(int n, int HD);
+int gnn_launch_keep_image(void* kimg, int n, int HD, float p, uint32_t k0, uint32_t k1, uint32_t step, uint32_t row0,
+                          const int* stepp, hipStream_t st);
+int gnn_launch_dense_bwd(const void* dY2, const float* W2, const void* H1, void* dP1, int n, int HD, int C, int ldc,
+                         float p, hipStream_t st);
+int gnn_fused_bwd_blocks(int n);
+int gnn_fused_bwd_width(int K);
+int gnn_fused_bwd_supported(int K, int HD, int C);
+int gnn_launch_fused_bwd(const void* AX, const void* dY2, const float* W1, const float* b1, const float* W2,
+                         const void* kimg, float* gpart, int n, int F, int ldx, int HD, int C, int ldc, float p,
+                         hipStream_t st);
+
+// ---- gnn_linear.hip: generic fused dense layers.  The launchers return the code to
+// Python: 0 ok, -1 no variant, -3 bad shape, -4 row ids / scales do not fit
+int gnn_lin_fwd_kc_wanted(int K, int N, int ldy);
+int gnn_launch_lin_fwd(const void* x1, int ld1, int K1, const void* x2, int ld2, int K2, const float* W, int N,
+                       const float* bias, void* Y, int ldy, int n, int relu, float p, uint32_t k0, uint32_t k1,
+                       uint32_t step, uint32_t row0, const int* stepp, const float* rscale, const int* idx1,
+                       void* wimg, float* Yf, int nsplit, int tk, hipStream_t st, int et);
+int gnn_launch_lin_bwd_data(const void* dY, int lddy, const void* Ym, int ldym, float mscale, int N, const float* W,
+                            int K1, int K2, void* dX1, int ldx1, void* dX2, int ldx2, const float* rscale, int n,
+                            int dx1_f32, void* wimg, hipStream_t st);
+long gnn_lin_fwd_image_bytes(int K, int N, int ldy);
+long gnn_lin_bwd_image_bytes(int K, int N);
+int gnn_lin_wgrad_chunks(int n, int N, int K);
+int gnn_launch_lin_bwd_weight(const void* x1, int ld1, int K1, const void* x2, int ld2, int K2, const void* dY,
+                              int lddy, const void* Ym, int ldym, float mscale, int N, float* gpart, float* dW,
+                              float* db, int n, const int* idx1, hipStream_t st);
+
+// ---- gnn_gat.hip: graph attention forward / backward and the fused epoch's dense side
+int gnn_gat_row_ce_waves();
+int gnn_launch_gat_row_ce(const float* Z, int ldz, const float* bias, int C, const int* y, const uint8_t* mask,
+                          float inv_count, float* dZ, void* dZb, float* stats_part, float* bpart, float* stats,
+                          float* db, long n, hipStream_t st);
+int gnn_launch_gat_pack_grad(const float* dWh, const float* ds_src, const float* ds_dst, int HF, int K, void* dy,
+                             int ldy, long n, hipStream_t st);
+int gnn_launch_gat_fwd(const int* rowptr, const int* col, const void* Wh, const float* s_src, const float* s_dst,
+                       const int* dst_rows, float* out, float* lse, void* q, int n, int K, int Fh, int wbf,
+                       const float* bias, void* H, int ldh, float p, uint32_t k0, uint32_t k1, uint32_t step,
+                       const int* stepp, uint32_t row0, hipStream_t st);
+int gnn_gat_row_blocks();
+int gnn_launch_gat_rows(int act, const void* dout, int ldh, const float* out, const void* q, const float* lse,
+                        const float* s_dst, const int* dst_rows, float* rstat, float* ds_dst, void* dy, int ldy,
+                        void* dout_w, const float* bias, float* bpart, float* db, float p, uint32_t k0, uint32_t k1,
+                        uint32_t step, const int* stepp, uint32_t row0, int n, int K, int Fh, int wbf,
+                        hipStream_t st);
+int gnn_launch_gat_col(const int* rowptr_t, const int* col_t, const void* Wh, const float* s_src, const float* rstat,
+                       const void* dout, float* dWh, float* ds_src, void* dy, int ldy, int n, int K, int Fh, int wbf,
+                       hipStream_t st);
+
+// ---- gnn_halo.hip: halo row exchange between graph shards
+int gnn_launch_halo_rows(const void* src, long src_pitch, const long* src_idx, void* dst, long dst_pitch,
+                         const long* dst_idx, long rows, int words, int mode, hipStream_t st);
+
+// ---- gnn_sampler.hip: neighbour sampling, the mini-batch pipeline and its worker thread.
+// The per-level arguments (int* const* and friends) are host arrays of L device pointers.
+int gnn_launch_sample_neighbors(const int* rowptr, const int* col, const int* nodes, int n, int fanout,
+                                const int* out_ptr, int* out_col, uint32_t k0, uint32_t k1, uint32_t salt,
+                                hipStream_t st);
+long gnn_sample_blocks_scratch(int n, int L, const int* fan, const int* nd_max);
+long gnn_sample_flag_bytes(int n);
+int gnn_launch_sample_blocks(const int* rowptr, const int* col, int n, const int* seeds, int n_seeds, int L,
+                             const int* fan, const int* nd_max, int* const* optr, float* const* inv_deg,
+                             int* const* picks, int* const* local, int* const* src, int* const* rp_t,
+                             int* const* col_t, int* const* cnt_t, int* counts, uint8_t* flag, int* map,
+                             int* bscratch, uint32_t k0, uint32_t k1, uint32_t salt, hipStream_t st,
+                             int* counts_host);
+// the worker: create returns an opaque handle, add_slot the slot index or < 0, submit the
+// job's sequence number (>= 1) or <= 0, wait 0 or the first error any job hit
+void* gnn_sw_create(int device, hipStream_t st, const int* rowptr, const int* col, int n, int L, const int* fan,
+                    const int* nd_max, uint8_t* flag, int* map, int* bscratch, uint32_t k0, uint32_t k1);
+int gnn_sw_add_slot(void* h, int* const* optr, float* const* inv, int* const* picks, int* const* local,
+                    int* const* src, int* const* rp_t, int* const* col_t, int* const* cnt_t, int* counts, int* host);
+long gnn_sw_submit(void* h, int slot, const int* seeds, int n, uint32_t salt, const hipEvent_t* waits, int nw);
+int gnn_sw_wait(void* h, long seq, int slot, hipStream_t consumer);
+void gnn_sw_destroy(void* h);
+
+}  // extern "C"

@@ -2,8 +2,10 @@
 // Every device pointer crosses the boundary as an integer (tensor.data_ptr()),
 // every stream as the integer handle of torch.cuda.current_stream(); the
 // extension never allocates device memory itself, PyTorch's caching allocator
-// owns all buffers.
+// owns all buffers.  The launchers it calls are declared in cgnn_api.h, which also
+// explains their return codes.
 #include <hip/hip_runtime.h>
+#include "cgnn_api.h"
 #include "cgnn_common.h"
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -15,132 +17,14 @@
 
 namespace py = pybind11;
 
-extern "C" {
-int cgnn_mmd_supported_d(int);
-int cgnn_mmd_mfma_supported(int);
-int cgnn_mmd_mfma_row_blocks(int);
-int cgnn_launch_mmd_mfma_rows(int, int, const float*, const float*, const float*, const float*, float*, float*,
-                              int, int, int, int, float, int, int, hipStream_t, int);
-int cgnn_gen_supported_h(int);
-int cgnn_gen_bwd_blocks(int);
-size_t cgnn_gen_bwd_lds(int, int, int, int);
-int cgnn_launch_mmd_rows(int, int, const float*, const float*, float*, float*, int, int, int, int, int,
-                         float, int, int, hipStream_t, int);
-int cgnn_mmd_mirror_slots(int, int);
-int cgnn_launch_loss_finalize(const float*, int, float*, float*, float*, float, int, float*, int,
-                              const int*, int, int, hipStream_t);
-int cgnn_launch_gen_fwd(const int*, int, const float*, int, const float*, float*, float*, int, float*,
-                        const uint32_t*, const int*, int, int, int, int, int, hipStream_t, int);
-int cgnn_gen_bwd_variant(int, int, int, int);
-int cgnn_gen_staged_supported(int, int, int);
-size_t cgnn_gen_fwd_lds(int, int);
-int cgnn_staged_plan(int, int, int, int, int, int*);
-int cgnn_staged_tiles(int);
-int cgnn_launch_gen_noise(const int*, int, const uint32_t*, const int*, int, float*, int, int, int, int, int, int,
-                          hipStream_t);
-int cgnn_launch_gen_fwd_staged(const int*, int, const int*, int, const float*, int, const float*, float*,
-                               const float*, int, float*, int, int, int, int, int, int, int, hipStream_t, int);
-int cgnn_launch_gen_bwd_staged(const int*, int, const int*, int, const float*, int, const float*, const float*, int,
-                               const float*, int, int, int, int, int, int, int, int, float*, float*, hipStream_t,
-                               int);
-int cgnn_launch_gen_bwd(const int*, int, const float*, int, const float*, const float*, int,
-                        const float*, int, int, int, int, int, int, int, float*, hipStream_t);
-int cgnn_launch_adam(float*, float*, float*, const float*, int, const int*, int, int, const int*,
-                     int, float, float, float, float, int, hipStream_t);
-int cgnn_launch_init(float*, float*, float*, const int*, int, int, const uint32_t*, float, int,
-                     hipStream_t);
-int cgnn_launch_advance(int*, int, int, hipStream_t);
-void* cgnn_engine_create(const int*, const float*, const void* const*, hipStream_t);
-void cgnn_engine_destroy(void*);
-int cgnn_engine_gen_blocks(void*);
-int cgnn_engine_n_parts(void*);
-void cgnn_engine_init(void*);
-void cgnn_engine_tt(void*);
-void cgnn_engine_run(void*, int, int, int, int);
-// Fourier (random-feature) MMD
-int rff_launch_freqs(float*, const uint32_t*, const int*, int, int, int, int, int, int, hipStream_t);
-int rff_launch_fwd_bwd(int, const float*, const float*, const float*, float*, float*, float*, int,
-                       int, int, int, int, float, hipStream_t, int, float*, int);
-long rff_wide_scratch_floats(int, int, int);
-// GNN track
-int gnn_launch_spmm(const int*, const int*, const void*, void*, const float*, const float*, int,
-                    int, int, int, int, int, int, int, const float*, int, const float*, int, int, hipStream_t);
-int gnn_launch_spmm_fan(const int*, const int*, const void*, void*, const float*, int, int, int, int, long, long, int,
-                        hipStream_t);
-int gnn_launch_wspmm(const int*, const int*, const float*, const int*, const void*, void*, const float*, const float*,
-                     const float*, int, int, int, int, int, int, int, hipStream_t);
-int gnn_launch_sddmm(const int*, const int*, const void*, const void*, float*, const float*, const float*, int, int,
-                     int, int, int, hipStream_t);
-int gnn_launch_spmm_ce(const int*, const int*, const void*, const float*, const float*,
-                       const int*, const uint8_t*, float*, void*, const float*, int, int, int, int, int, float,
-                       const int*, int, hipStream_t);
-int gnn_launch_adam(float*, float*, float*, const float*, int, float, float, float, float, float, int*, unsigned*,
-                    int, hipStream_t);
-int gnn_launch_cast_bf16(const float*, void*, long, hipStream_t);
-int gnn_spmm_ce_blocks(int, int);
-int gnn_launch_ell_build(const int*, const int*, int*, int, hipStream_t);
-int gnn_launch_spmm_ell(const int*, const int*, const void*, void*, const float*, int, int, int, int, long,
-                        const int*, int, hipStream_t);
-int gnn_slab_sum(const float*, long, int, float*, int, float*, const int*, int*, hipStream_t);
-int gnn_launch_sample_neighbors(const int*, const int*, const int*, int, int, const int*, int*, uint32_t, uint32_t,
-                                uint32_t, hipStream_t);
-int gnn_launch_bias_relu_dropout(void*, const float*, long, int, int, float, uint32_t, uint32_t,
-                                 uint32_t, uint32_t, hipStream_t);
-int gnn_launch_relu_dropout_bwd(void*, const void*, long, float, hipStream_t);
-int gnn_launch_dense_fwd(const void*, const float*, const float*, const float*, const float*, void*, void*,
-                         int, int, int, int, int, int, float, uint32_t, uint32_t, uint32_t, uint32_t,
-                         const int*, void*, hipStream_t);
-long gnn_keep_image_halfwords(int, int);
-int gnn_launch_keep_image(void*, int, int, float, uint32_t, uint32_t, uint32_t, uint32_t, const int*, hipStream_t);
-int gnn_launch_gat_fwd(const int*, const int*, const void*, const float*, const float*, const int*, float*, float*,
-                       void*, int, int, int, int, const float*, void*, int, float, uint32_t, uint32_t, uint32_t,
-                       const int*, uint32_t, hipStream_t);
-int gnn_gat_row_blocks();
-int gnn_launch_gat_rows(int, const void*, int, const float*, const void*, const float*, const float*, const int*,
-                        float*, float*, void*, int, void*, const float*, float*, float*, float, uint32_t, uint32_t,
-                        uint32_t, const int*, uint32_t, int, int, int, int, hipStream_t);
-int gnn_launch_gat_col(const int*, const int*, const void*, const float*, const float*, const void*, float*, float*,
-                       void*, int, int, int, int, int, hipStream_t);
-int gnn_gat_row_ce_waves();
-int gnn_launch_gat_row_ce(const float*, int, const float*, int, const int*, const uint8_t*, float, float*, void*,
-                          float*, float*, float*, float*, long, hipStream_t);
-int gnn_launch_gat_pack_grad(const float*, const float*, const float*, int, int, void*, int, long, hipStream_t);
-int gnn_launch_halo_rows(const void*, long, const long*, void*, long, const long*, long, int, int, hipStream_t);
-long gnn_sample_blocks_scratch(int, int, const int*, const int*);
-long gnn_sample_flag_bytes(int);
-int gnn_launch_sample_blocks(const int*, const int*, int, const int*, int, int, const int*, const int*, int* const*,
-                             float* const*, int* const*, int* const*, int* const*, int* const*, int* const*,
-                             int* const*, int*, uint8_t*, int*, int*, uint32_t, uint32_t, uint32_t, hipStream_t,
-                             int*);
-void* gnn_sw_create(int, hipStream_t, const int*, const int*, int, int, const int*, const int*, uint8_t*, int*, int*,
-                    uint32_t, uint32_t);
-int gnn_sw_add_slot(void*, int* const*, float* const*, int* const*, int* const*, int* const*, int* const*,
-                    int* const*, int* const*, int*, int*);
-long gnn_sw_submit(void*, int, const int*, int, uint32_t, const hipEvent_t*, int);
-int gnn_sw_wait(void*, long, int, hipStream_t);
-void gnn_sw_destroy(void*);
-int gnn_fused_bwd_blocks(int);
-int gnn_fused_bwd_width(int);
-int gnn_fused_bwd_supported(int, int, int);
-int gnn_launch_fused_bwd(const void*, const void*, const float*, const float*, const float*, const void*, float*,
-                         int, int, int, int, int, int, float, hipStream_t);
-int gnn_launch_dense_bwd(const void*, const float*, const void*, void*, int, int, int, int, float,
-                         hipStream_t);
-int gnn_launch_lin_fwd(const void*, int, int, const void*, int, int, const float*, int, const float*, void*, int,
-                       int, int, float, uint32_t, uint32_t, uint32_t, uint32_t, const int*, const float*,
-                       const int*, void*, float*, int, int, hipStream_t, int);
-int gnn_launch_lin_bwd_data(const void*, int, const void*, int, float, int, const float*, int, int, void*, int,
-                            void*, int, const float*, int, int, void*, hipStream_t);
-long gnn_lin_fwd_image_bytes(int, int, int);
-int gnn_lin_fwd_kc_wanted(int, int, int);
-long gnn_lin_bwd_image_bytes(int, int);
-int gnn_lin_wgrad_chunks(int, int, int);
-int gnn_launch_lin_bwd_weight(const void*, int, int, const void*, int, int, const void*, int, const void*, int,
-                              float, int, float*, float*, float*, int, const int*, hipStream_t);
-}
-
 static inline hipStream_t S(uint64_t s) { return reinterpret_cast<hipStream_t>(s); }
 template <class T> static inline T* Pt(uint64_t p) { return reinterpret_cast<T*>(p); }
+// a per-level list of device addresses as the host array of pointers the sampler takes
+template <class T> static std::vector<T*> Pts(const std::vector<uint64_t>& v) {
+  std::vector<T*> o(v.size());
+  for (size_t i = 0; i < v.size(); ++i) o[i] = reinterpret_cast<T*>(v[i]);
+  return o;
+}
 
 static void chk(int rc, const char* what) {
   if (rc != 0) throw std::runtime_error(std::string(what) + ": HIP launch failed (code " + std::to_string(rc) + ")");
@@ -472,14 +356,9 @@ PYBIND11_MODULE(_hip, m) {
     if (nd_max.size() != L || optr.size() != L || inv_deg.size() != L || picks.size() != L || local.size() != L ||
         src.size() != L || rp_t.size() != L || col_t.size() != L || cnt_t.size() != L)
       throw std::runtime_error("gnn_sample_blocks: per-level lists differ in length");
-    auto ip = [](const std::vector<uint64_t>& v) {
-      std::vector<int*> o(v.size());
-      for (size_t i = 0; i < v.size(); ++i) o[i] = reinterpret_cast<int*>(v[i]);
-      return o;
-    };
-    std::vector<float*> inv(L);
-    for (size_t i = 0; i < L; ++i) inv[i] = reinterpret_cast<float*>(inv_deg[i]);
-    auto a = ip(optr), b = ip(picks), c = ip(local), d = ip(src), e = ip(rp_t), f = ip(col_t), g = ip(cnt_t);
+    auto inv = Pts<float>(inv_deg);
+    auto a = Pts<int>(optr), b = Pts<int>(picks), c = Pts<int>(local), d = Pts<int>(src), e = Pts<int>(rp_t),
+         f = Pts<int>(col_t), g = Pts<int>(cnt_t);
     chk(gnn_launch_sample_blocks(Pt<const int>(rowptr), Pt<const int>(col), n, Pt<const int>(seeds), n_seeds,
                                  (int)L, fan.data(), nd_max.data(), a.data(), inv.data(), b.data(), c.data(),
                                  d.data(), e.data(), f.data(), g.data(), Pt<int>(counts), Pt<uint8_t>(flag),
@@ -523,14 +402,9 @@ PYBIND11_MODULE(_hip, m) {
     if (inv_deg.size() != L || picks.size() != L || local.size() != L || src.size() != L || rp_t.size() != L ||
         col_t.size() != L || cnt_t.size() != L)
       throw std::runtime_error("gnn_sw_add_slot: per-level lists differ in length");
-    auto ip = [](const std::vector<uint64_t>& v) {
-      std::vector<int*> o(v.size());
-      for (size_t i = 0; i < v.size(); ++i) o[i] = reinterpret_cast<int*>(v[i]);
-      return o;
-    };
-    std::vector<float*> inv(L);
-    for (size_t i = 0; i < L; ++i) inv[i] = reinterpret_cast<float*>(inv_deg[i]);
-    auto a = ip(optr), b = ip(picks), c = ip(local), d = ip(src), e = ip(rp_t), f = ip(col_t), g = ip(cnt_t);
+    auto inv = Pts<float>(inv_deg);
+    auto a = Pts<int>(optr), b = Pts<int>(picks), c = Pts<int>(local), d = Pts<int>(src), e = Pts<int>(rp_t),
+         f = Pts<int>(col_t), g = Pts<int>(cnt_t);
     const int r = gnn_sw_add_slot((void*)(uintptr_t)h, a.data(), inv.data(), b.data(), c.data(), d.data(), e.data(),
                                   f.data(), g.data(), Pt<int>(counts), Pt<int>(host));
     if (r < 0) throw std::runtime_error("gnn_sw_add_slot failed");
@@ -577,7 +451,7 @@ PYBIND11_MODULE(_hip, m) {
                                 Pt<const float>(w2), Pt<const void>(kimg), Pt<float>(gpart), n, F, ldx, HD, C, ldc,
                                 p, S(st));
   });
-  // generic fused dense layers (gnn_linear.hip); return codes: 0 ok, -1 no variant, -3 bad shape
+  // generic fused dense layers (gnn_linear.hip); the launcher's code goes back to Python
   m.def("gnn_lin_fwd", [](uint64_t x1, int ld1, int K1, uint64_t x2, int ld2, int K2, uint64_t w, int N, uint64_t b,
                           uint64_t y, int ldy, int n, int relu, float p, uint32_t k0, uint32_t k1, uint32_t step,
                           uint32_t row0, uint64_t stepp, uint64_t rscale, uint64_t st, uint64_t idx1, uint64_t wimg,

@@ -15,44 +15,10 @@
 // search candidate only requires rewriting the program/data/key buffers and
 // re-running init -- the captured graphs stay valid.
 #include "cgnn_common.h"
+#include "cgnn_api.h"
 #include <map>
 #include <stdexcept>
 #include <string>
-
-extern "C" {
-int cgnn_launch_mmd(int, int, const float*, const float*, float*, float*, int, int, int, int, int,
-                    float, hipStream_t, int);
-int cgnn_launch_mmd_mfma(int, int, const float*, const float*, const float*, const float*, float*, float*,
-                         int, int, int, int, float, hipStream_t);
-int cgnn_mmd_mfma_row_blocks(int);
-int cgnn_launch_loss_finalize(const float*, int, float*, float*, float*, float, int, float*, int,
-                              const int*, int, int, hipStream_t);
-int cgnn_launch_gen_fwd(const int*, int, const float*, int, const float*, float*, float*, int, float*,
-                        const uint32_t*, const int*, int, int, int, int, int, hipStream_t, int);
-int cgnn_launch_gen_bwd(const int*, int, const float*, int, const float*, const float*, int,
-                        const float*, int, int, int, int, int, int, int, float*, hipStream_t);
-int cgnn_staged_tiles(int);
-int cgnn_launch_gen_noise(const int*, int, const uint32_t*, const int*, int, float*, int, int, int, int, int, int,
-                          hipStream_t);
-int cgnn_launch_gen_fwd_staged_draw(const int*, int, const int*, int, const float*, int, const float*, float*, float*,
-                                    int, float*, int, int, int, int, int, int, int, hipStream_t, int, const uint32_t*,
-                                    const int*, int, int);
-int cgnn_launch_gen_fwd_staged(const int*, int, const int*, int, const float*, int, const float*, float*,
-                               const float*, int, float*, int, int, int, int, int, int, int, hipStream_t, int);
-int cgnn_launch_gen_bwd_staged(const int*, int, const int*, int, const float*, int, const float*, const float*, int,
-                               const float*, int, int, int, int, int, int, int, int, float*, float*, hipStream_t,
-                               int);
-int cgnn_mmd_supported_d(int);
-int cgnn_gen_bwd_blocks(int);
-int cgnn_launch_adam(float*, float*, float*, const float*, int, const int*, int, int, const int*,
-                     int, float, float, float, float, int, hipStream_t);
-int cgnn_launch_init(float*, float*, float*, const int*, int, int, const uint32_t*, float, int,
-                     hipStream_t);
-int cgnn_launch_advance(int*, int, int, hipStream_t);
-int rff_launch_freqs(float*, const uint32_t*, const int*, int, int, int, int, int, int, hipStream_t);
-int rff_launch_fwd_bwd(int, const float*, const float*, const float*, float*, float*, float*, int,
-                       int, int, int, int, float, hipStream_t, int, float*, int);
-}
 
 namespace cgnn {
 

@@ -22,6 +22,7 @@
 //   params, m, v      : [R][P]       per-node blocks W1[nin][H], b1[H], W2[H], b2.
 //   prog              : [R][stride]  int32 "DAG program", see engine/program.py.
 #include "cgnn_common.h"
+#include "cgnn_api.h"
 #include <cstdlib>
 
 using namespace cgnn;
@@ -756,8 +757,6 @@ extern "C" size_t cgnn_gen_bwd_lds(int H, int max_in, int D, int prog_stride) {
   return sizeof(float) * ((size_t)GEN_BWD_BS * (HE + ((max_in + 2) | 1) + 2 * (size_t)D) + 128 +
                           (size_t)(max_in + 1) * HE);
 }
-
-extern "C" int cgnn_staged_plan(int, int, int, int, int, int*);
 
 // 1: the specialised per-sample kernel (compiled H, LDS sample state fits), 2: the
 // level-scheduled kernels of cgnn_staged.hip, 0: neither fits (the caller trains this

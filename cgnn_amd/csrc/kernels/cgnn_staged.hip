@@ -33,6 +33,7 @@
 // Blocks are dealt XCD-contiguously (xcd_remap), so the tiles of one model share an
 // L2 and its weight stream.
 #include "cgnn_common.h"
+#include "cgnn_api.h"
 #include <algorithm>
 
 using namespace cgnn;

@@ -22,6 +22,7 @@
 // The weights (W1^T, W2^T, b1) live in LDS for the whole persistent block; rows are
 // processed in 32-row tiles, one tile per wave at a time, grid-strided.
 #include "cgnn_common.h"
+#include "cgnn_api.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>

@@ -20,6 +20,7 @@
 //                    into the projection-gradient operand dy.
 // Arithmetic fp32, fixed summation orders (deterministic).
 #include "cgnn_common.h"
+#include "cgnn_api.h"
 #include <algorithm>
 #include <cmath>
 

@@ -19,6 +19,7 @@
 // sort-based index_put_(accumulate=True), which dominated the emulated papers100M
 // epoch (13 % for the kernel alone, plus its sorts and checks).
 #include <hip/hip_runtime.h>
+#include "cgnn_api.h"
 #include <cstdint>
 
 __global__ __launch_bounds__(256) void halo_rows_kernel(const uint8_t* __restrict__ src, long src_pitch,

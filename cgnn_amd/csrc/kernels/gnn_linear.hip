@@ -34,6 +34,7 @@
 // per-chunk fp32 slabs are summed in a fixed order by lin_reduce (deterministic,
 // no atomics).
 #include "cgnn_common.h"
+#include "cgnn_api.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>

@@ -11,6 +11,7 @@
 //                             does not depend on the batch it is in or on the
 //                             thread that draws it).
 #include "cgnn_common.h"
+#include "cgnn_api.h"
 #include <algorithm>
 #include <condition_variable>
 #include <deque>

@@ -18,6 +18,7 @@
 // broadcast inside the sub-group with ds_bpermute; four gathered rows are kept
 // in flight per lane.  Accumulation is fp32; storage is bf16.
 #include "cgnn_common.h"
+#include "cgnn_api.h"
 #include "gnn_gather.h"
 #include <algorithm>
 #include <cmath>

@@ -25,6 +25,7 @@
 // edge load sits behind the row's e1 > e0 test and is clamped into [e0, e1)), so a graph
 // without edges may pass null pointers for them.
 #include "cgnn_common.h"
+#include "cgnn_api.h"
 #include "gnn_gather.h"
 #include <algorithm>
 
@@ -319,9 +320,8 @@ static int wspmm_launch(const int* rowptr, const int* col, const float* val, con
   return -1;
 }
 
-// No allocation and no synchronisation: capturable into a hipGraph.  Return codes: -3 a
-// row stride that is no multiple of 8 or narrower than F, -5 an (X, Y) type pair that is
-// not compiled, else the launch's HIP error.
+// No allocation and no synchronisation: capturable into a hipGraph.  Return codes: see
+// cgnn_api.h.
 extern "C" int gnn_launch_wspmm(const int* rowptr, const int* col, const float* val, const int* eperm,
                                 const void* X, void* Y, const float* rscale, const float* cscale,
                                 const float* bias, int n_rows, int F, int ldx, int ldy, int xt, int yt, int relu,
@@ -364,7 +364,7 @@ static int sddmm_dispatch(const int* rowptr, const int* col, const void* A, cons
   return (int)hipGetLastError();
 }
 
-// A and B share the storage type t.  Same return codes as gnn_launch_wspmm.
+// A and B share the storage type t.
 extern "C" int gnn_launch_sddmm(const int* rowptr, const int* col, const void* A, const void* B, float* out,
                                 const float* rscale, const float* cscale, int n_rows, int F, int lda, int ldb,
                                 int t, hipStream_t st) {

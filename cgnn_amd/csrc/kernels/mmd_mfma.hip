@@ -20,6 +20,7 @@
 //      from the transposed LDS image [d][j] at those j -- no lane movement.
 //   dL/dp_i = 4/N^2 (G_i - p_i sum_j W_ij)
 #include "cgnn_common.h"
+#include "cgnn_api.h"
 
 using namespace cgnn;
 

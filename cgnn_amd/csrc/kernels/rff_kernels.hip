@@ -15,6 +15,7 @@
 // Default: matrix-core kernels (below); the vector kernels (one feature / one sample
 // per thread) remain for W images too large for LDS (and for A/B, force_valu).
 #include "cgnn_common.h"
+#include "cgnn_api.h"
 #include <cstdlib>
 
 using namespace cgnn;

@@ -26,11 +26,8 @@ import torch
 from .. import native
 from ..utils import checks
 from .data import GraphData
+from .ops import _st
 from .sage import transpose_csr
-
-
-def _st(t):
-    return torch._C._cuda_getCurrentRawStream(t.get_device())
 
 
 class GraphCSR:

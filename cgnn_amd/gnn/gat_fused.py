@@ -52,18 +52,7 @@ from .. import native
 from ..utils.philox import model_key
 from . import ops
 from .linear import lin_bwd_data, lin_bwd_weight, lin_fwd
-
-
-def _st(t):
-    return torch._C._cuda_getCurrentRawStream(t.get_device())
-
-
-def _ru8(x):
-    return (x + 7) // 8 * 8
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else 0
+from .ops import _ptr, _ru8, _st
 
 
 # ------------------------------------------------------------------ elementwise ops

@@ -57,10 +57,7 @@ from ..parallel import dist as pdist
 from ..utils.philox import model_key
 from . import ops
 from .data import GraphData, partition_rows
-
-
-def _ru8(x):
-    return (x + 7) // 8 * 8
+from .ops import _ru8
 
 
 def _ru(x, m):

@@ -24,7 +24,7 @@ import torch
 
 from .. import native
 from ..utils import checks
-from .ops import _st, _step_args, _step_value, dropout_keep_mask
+from .ops import _ptr, _st, _step_args, _step_value, dropout_keep_mask
 
 _GPART = {}
 _WIMG = {}
@@ -40,10 +40,6 @@ def _wimg(dev, nbytes):
     if buf is None:
         buf = _WIMG[key] = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
     return buf
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else 0
 
 
 def _check(rc, what):

@@ -21,6 +21,14 @@ def _st(t):
     return torch._C._cuda_getCurrentRawStream(t.get_device())
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None else 0
+
+
+def _ru8(x):
+    return (x + 7) // 8 * 8
+
+
 def _row_ids(rowptr):
     n = rowptr.numel() - 1
     counts = (rowptr[1:] - rowptr[:-1]).to(torch.int64)
