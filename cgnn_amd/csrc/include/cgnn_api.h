@@ -139,6 +139,15 @@ int gnn_launch_wspmm(const int* rowptr, const int* col, const float* val, const 
 int gnn_launch_sddmm(const int* rowptr, const int* col, const void* A, const void* B, float* out, const float* rscale,
                      const float* cscale, int n_rows, int F, int lda, int ldb, int t, hipStream_t st);
 
+// ---- gnn_pool.hip: max / min neighbour pooling with the arg edge index, and its gradient
+// over the transposed CSR.  t / tdy / tdx: storage types; arg may be null in the forward;
+// -3 for a bad stride or a missing pointer, -5 for a type (pair) that is not compiled
+int gnn_launch_pool_fwd(const int* rowptr, const int* col, const void* X, void* Y, int* arg, int n_rows, int F,
+                        int ldx, int ldy, int ldarg, int t, int is_min, hipStream_t st);
+int gnn_launch_pool_bwd(const int* rowptr_t, const int* col_t, const int* eperm, const int* arg, int ldarg,
+                        const void* dY, int lddy, void* dX, int lddx, int n_src, int F, int tdy, int tdx,
+                        hipStream_t st);
+
 // ---- gnn_dense.hip: the fused two-layer dense GCN kernels.  The launchers return -1
 // when no compiled variant covers (F, HD, C); Python then raises
 int gnn_launch_dense_fwd(const void* AX, const float* W1, const float* b1, const float* W2, const float* dinv,

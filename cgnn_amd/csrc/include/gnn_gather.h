@@ -315,5 +315,74 @@ __device__ __forceinline__ void gather_sum_x2(const int* __restrict__ col, const
   }
 }
 
+// ---- per-lane pieces of the kernels that treat each gathered row on its own (gnn_wspmm.hip,
+// gnn_pool.hip)
+
+// 8 features at element offset `off` as raw registers: one 16-byte load for bf16 / fp16
+// (b unused), two for fp32
+template <int XT>
+struct Raw8 {
+  uint4 a, b;
+};
+
+template <int XT>
+__device__ __forceinline__ Raw8<XT> load_raw8(const void* X, size_t off) {
+  Raw8<XT> r;
+  if (XT == 0) {
+    const uint4* p = reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(X) + off);
+    r.a = p[0];
+    r.b = p[1];
+  } else {
+    r.a = load_raw16(X, off);
+    r.b = r.a;
+  }
+  return r;
+}
+
+template <int XT>
+__device__ __forceinline__ void raw8_to_f32(const Raw8<XT>& r, float* f) {
+  if (XT == 1) {
+    bf16x8_to_f32(r.a, f);
+  } else if (XT == 2) {
+    const f16x8 v = __builtin_bit_cast(f16x8, r.a);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) f[q] = (float)v[q];
+  } else {
+    f[0] = __uint_as_float(r.a.x); f[1] = __uint_as_float(r.a.y);
+    f[2] = __uint_as_float(r.a.z); f[3] = __uint_as_float(r.a.w);
+    f[4] = __uint_as_float(r.b.x); f[5] = __uint_as_float(r.b.y);
+    f[6] = __uint_as_float(r.b.z); f[7] = __uint_as_float(r.b.w);
+  }
+}
+
+// v of lane k + u of the sub-group, u = 0..N-1 (k a multiple of N).  L = 16: the sub-group
+// is one DPP row, the ids move by row broadcast (a VALU move, no LDS permute)
+template <int L, int N>
+__device__ __forceinline__ void sub_bcast(int v, int sub_base, int k, int* out) {
+  if (L == 16 && N == 8) {
+    if (k == 0) row_bcast8<0>(v, out);
+    else row_bcast8<8>(v, out);
+  } else {
+#pragma unroll
+    for (int u = 0; u < N; ++u) out[u] = __shfl(v, sub_base + k + u, 64);
+  }
+}
+
+template <int YT>
+__device__ __forceinline__ void store8(void* Y, size_t off, const float* y) {
+  if (YT == 1) {
+    *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(Y) + off) = f32x8_to_bf16(y);
+  } else if (YT == 2) {
+    f16x8 o;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) o[q] = (_Float16)y[q];
+    *reinterpret_cast<f16x8*>(reinterpret_cast<uint16_t*>(Y) + off) = o;
+  } else {
+    float4* p = reinterpret_cast<float4*>(reinterpret_cast<float*>(Y) + off);
+    p[0] = make_float4(y[0], y[1], y[2], y[3]);
+    p[1] = make_float4(y[4], y[5], y[6], y[7]);
+  }
+}
+
 }  // namespace gather
 }  // namespace cgnn

@@ -207,6 +207,24 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("rowptr"), py::arg("col"), py::arg("a"), py::arg("b"), py::arg("out"), py::arg("rscale"),
      py::arg("cscale"), py::arg("n_rows"), py::arg("F"), py::arg("ld_a"), py::arg("ld_b"), py::arg("type"),
      py::arg("st"));
+  // max / min neighbour pooling and its gradient (gnn_pool.hip)
+  m.def("gnn_pool_fwd", [](uint64_t rowptr, uint64_t col, uint64_t x, uint64_t y, uint64_t arg, int n_rows, int F,
+                           int ld_x, int ld_y, int ld_arg, int type, int is_min, uint64_t st) {
+    chk(gnn_launch_pool_fwd(Pt<const int>(rowptr), Pt<const int>(col), Pt<const void>(x), Pt<void>(y), Pt<int>(arg),
+                            n_rows, F, ld_x, ld_y, ld_arg, type, is_min, S(st)),
+        "gnn_pool_fwd");
+  }, py::arg("rowptr"), py::arg("col"), py::arg("x"), py::arg("y"), py::arg("arg"), py::arg("n_rows"), py::arg("F"),
+     py::arg("ld_x"), py::arg("ld_y"), py::arg("ld_arg"), py::arg("type"), py::arg("is_min"), py::arg("st"));
+  m.def("gnn_pool_bwd", [](uint64_t rowptr_t, uint64_t col_t, uint64_t eperm, uint64_t arg, int ld_arg, uint64_t dy,
+                           int ld_dy, uint64_t dx, int ld_dx, int n_src, int F, int dy_type, int dx_type,
+                           uint64_t st) {
+    chk(gnn_launch_pool_bwd(Pt<const int>(rowptr_t), Pt<const int>(col_t), Pt<const int>(eperm), Pt<const int>(arg),
+                            ld_arg, Pt<const void>(dy), ld_dy, Pt<void>(dx), ld_dx, n_src, F, dy_type, dx_type,
+                            S(st)),
+        "gnn_pool_bwd");
+  }, py::arg("rowptr_t"), py::arg("col_t"), py::arg("eperm"), py::arg("arg"), py::arg("ld_arg"), py::arg("dy"),
+     py::arg("ld_dy"), py::arg("dx"), py::arg("ld_dx"), py::arg("n_src"), py::arg("F"), py::arg("dy_type"),
+     py::arg("dx_type"), py::arg("st"));
   m.def("gnn_spmm_fan", [](uint64_t rowptr, uint64_t col, uint64_t x, uint64_t y, uint64_t rscale, int n_rows, int F,
                            int ldx, int ldy, long n_x_rows, long nnz, int max_deg, uint64_t st) {
     chk(gnn_launch_spmm_fan(Pt<const int>(rowptr), Pt<const int>(col), Pt<const void>(x), Pt<void>(y),

@@ -13,6 +13,8 @@ track, not in the reference.
 * ``WeightedGraph`` / ``weighted_aggregate`` -- the same layers over a directed graph
   with one value per edge (``ops.wspmm``): the backward runs over the transposed CSR,
   and the edge values receive a gradient (``ops.sddmm``) when they require one.
+* ``pool_aggregate`` -- element-wise max / min over each node's neighbours
+  (``ops.pool``), the gradient routed through the saved edge index (``ops.pool_bwd``).
 
 Everything runs on the same ``ops.spmm`` as the fused 2-layer trainer (HIP on
 GPU tensors, PyTorch index ops on CPU tensors); dense products are hipBLASLt
@@ -40,10 +42,19 @@ class NormGraph:
     def __init__(self, rowptr: torch.Tensor, col: torch.Tensor, dinv: torch.Tensor):
         self.rowptr, self.col, self.dinv = rowptr.contiguous(), col.contiguous(), dinv.contiguous()
         self.n = rowptr.numel() - 1
+        self._tperm = None
 
     @classmethod
     def from_data(cls, g) -> "NormGraph":
         return cls(g.rowptr, g.col, g.dinv)
+
+    def transposed_perm(self):
+        """``(rowptr_t, col_t, eperm)`` of the transpose, as ``WeightedGraph.transposed``
+        (the pooling backward needs the edge permutation).  Built once."""
+        if self._tperm is None:
+            from .sage import transpose_csr
+            self._tperm = transpose_csr(self.rowptr, self.col, self.n, with_perm=True)
+        return self._tperm
 
 
 def aggregate(x: torch.Tensor, g: NormGraph, prescaled: bool = False, bias=None, relu: bool = False):
@@ -135,6 +146,8 @@ class WeightedGraph:
             self._t = transpose_csr(self.rowptr, self.col, self.n_src, with_perm=True)
         return self._t
 
+    transposed_perm = transposed
+
     @classmethod
     def from_edges(cls, n: int, src, dst, weight=None, self_loops: Optional[float] = 1.0,
                    normalize: Optional[str] = "sym", device=None) -> "WeightedGraph":
@@ -218,6 +231,37 @@ def weighted_aggregate(x: torch.Tensor, g: WeightedGraph, val: Optional[torch.Te
     the edge values; a tensor that requires grad receives d loss / d val (fp32), which is how
     edge weights are learned or explained."""
     return _WeightedAggregate.apply(x, g.val if val is None else val, g)
+
+
+class _PoolAggregate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, g, reduce):
+        F = x.shape[1]
+        xs = pad_cols(x).contiguous()
+        y, arg = ops.pool(g.rowptr, g.col, xs, F, reduce=reduce, with_arg=ctx.needs_input_grad[0],
+                          ld_out=xs.shape[1])
+        ctx.g, ctx.F = g, F
+        ctx.save_for_backward(arg)
+        return y[:, :F] if y.shape[1] != F else y
+
+    @staticmethod
+    def backward(ctx, gy):
+        arg, = ctx.saved_tensors
+        rp_t, col_t, eperm = ctx.g.transposed_perm()
+        F = ctx.F
+        dyp = pad_cols(gy).contiguous()
+        dx = ops.pool_bwd(rp_t, col_t, eperm, arg, dyp, F, out_dtype=gy.dtype, ld_out=dyp.shape[1])
+        return (dx[:, :F] if dx.shape[1] != F else dx), None, None
+
+
+def pool_aggregate(x: torch.Tensor, g, reduce: str = "max") -> torch.Tensor:
+    """Element-wise max / min of ``x`` over each node's neighbours (``ops.pool``); an empty
+    neighbourhood gives 0.  ``g``: anything with ``rowptr``, ``col`` (row = destination,
+    column = source) and ``transposed_perm()`` -- a :class:`WeightedGraph` (its values and
+    scales are ignored), a :class:`NormGraph`, a ``sage.Block``.  The gradient goes to the
+    element that supplied each result (the first edge on ties), through the saved edge index
+    and a gather over the transposed CSR (``ops.pool_bwd``): deterministic, no atomics."""
+    return _PoolAggregate.apply(x, g, reduce)
 
 
 class _WeightedGCNLayer(torch.autograd.Function):

@@ -2,8 +2,8 @@
 
 The CPU branch is the numerical reference used by the tests (and lets the
 models run in CI); on a GPU the HIP kernels of csrc/kernels/gnn_sparse.hip (and
-gnn_wspmm.hip for the edge-weighted ops) are mandatory -- a missing extension raises
-instead of silently falling back.
+gnn_wspmm.hip for the edge-weighted ops, gnn_pool.hip for max / min pooling) are
+mandatory -- a missing extension raises instead of silently falling back.
 """
 from __future__ import annotations
 
@@ -219,6 +219,122 @@ def sddmm(rowptr, col, A, B, F, rscale=None, cscale=None, out=None):
     if cscale is not None:
         d = d * cscale[j].to(at)
     out[:nnz] = d.to(out.dtype)
+    return out
+
+
+def _pool_reduce(reduce) -> bool:
+    if reduce not in ("max", "min"):
+        raise ValueError("pool: reduce must be 'max' or 'min', got %r" % (reduce,))
+    return reduce == "min"
+
+
+def _check_arg(arg, n, F, what):
+    if arg.dtype != torch.int32:
+        raise ValueError("CGNN_CHECK: %s: arg must be int32, got %s" % (what, arg.dtype))
+    if arg.dim() != 2 or arg.shape[1] % 8 or arg.shape[1] < F:
+        raise ValueError("CGNN_CHECK: %s: arg row stride %s must be a multiple of 8 and cover F = %d"
+                         % (what, tuple(arg.shape[1:]), F))
+    checks.rows(arg, n, what + " arg")
+
+
+def pool(rowptr, col, X, F, reduce="max", out=None, arg=None, with_arg=True, ld_out=None):
+    """Element-wise max / min over each row's neighbours (gnn_pool.hip, pool_fwd_kernel):
+    ``Y[i,f] = reduce_{e in row i} X[col[e], f]`` and ``arg[i,f]`` = the edge index (global,
+    int32) that supplied it.  Returns ``(Y, arg)``; ``arg`` is None with ``with_arg=False``.
+    Edges are scanned in CSR order and a candidate replaces the running best only when it is
+    strictly better or when it is NaN and the best is not: ties go to the first edge holding
+    the value, a NaN propagates (arg = the first NaN edge).  An empty row and the padding
+    columns ``F <= f < ld`` give ``Y = 0``, ``arg = -1``.  Y has X's storage type (fp32 /
+    bf16 / fp16 on the GPU; fp64 too on CPU tensors): it is a copy of an input element, so
+    the result is exact."""
+    is_min = _pool_reduce(reduce)
+    n = rowptr.numel() - 1
+    ldo = ld_out or X.shape[1]
+    if out is None:
+        out = torch.empty(n, ldo, dtype=X.dtype, device=X.device)
+    if arg is None and with_arg:
+        arg = torch.empty(n, out.shape[1], dtype=torch.int32, device=X.device)
+    if not with_arg:
+        arg = None
+    if checks.enabled():
+        checks.csr(rowptr, col, X.shape[0], "pool")
+        checks.rows(out, n, "pool out")
+        if arg is not None:
+            _check_arg(arg, n, F, "pool")
+    if out.dtype != X.dtype:
+        raise TypeError("pool: the output has the input's dtype, got %s for %s" % (out.dtype, X.dtype))
+    if X.is_cuda:
+        if arg is not None and arg.dtype != torch.int32:
+            raise TypeError("pool: arg must be int32")
+        if not (X.is_contiguous() and out.is_contiguous() and (arg is None or arg.is_contiguous())):
+            raise ValueError("pool: contiguous operands expected")
+        native.hip().gnn_pool_fwd(rowptr.data_ptr(), col.data_ptr(), X.data_ptr(), out.data_ptr(), _ptr(arg), n, F,
+                                  X.shape[1], out.shape[1], arg.shape[1] if arg is not None else 0,
+                                  dtype_code(X.dtype), int(is_min), _st(X))
+        return out, arg
+    rp = rowptr.long()
+    deg = rp[1:] - rp[:-1]
+    best = torch.zeros(n, F, dtype=X.dtype)
+    bi = torch.full((n, F), -1, dtype=torch.int64)
+    for k in range(int(deg.max()) if n else 0):          # the k-th edge of every row that has one
+        r = torch.nonzero(deg > k).flatten()
+        e = rp[r] + k
+        c, b = X[col[e].long(), :F], best[r]
+        if k == 0:
+            take = torch.ones_like(c, dtype=torch.bool)
+        else:
+            take = ((c < b) if is_min else (c > b)) | (torch.isnan(c) & ~torch.isnan(b))
+        best[r] = torch.where(take, c, b)
+        bi[r] = torch.where(take, e[:, None].expand_as(c), bi[r])
+    out[:n].zero_()
+    out[:n, :F] = best
+    if arg is not None:
+        arg[:n].fill_(-1)
+        arg[:n, :F] = bi.to(arg.dtype)
+    return out, arg
+
+
+def pool_bwd(rowptr_t, col_t, eperm, arg, dY, F, out=None, out_dtype=None, ld_out=None):
+    """The gradient of ``pool`` as a gather over the transposed CSR (gnn_pool.hip,
+    pool_bwd_kernel): ``dX[j,f] = sum_t (arg[i,f] == e ? dY[i,f] : 0)`` over the transposed
+    edges t of source row j, ``i = col_t[t]`` the destination and ``e = eperm[t]`` the forward
+    edge (``transpose_csr(..., with_perm=True)``).  Edge indices are compared, not node ids,
+    so a source repeated in a row is counted once.  The terms are added in fp32 (fp64 for
+    fp64 on the CPU) as one chain in transposed-edge order: bit-identical from run to run,
+    no atomics.  The GPU compiles the (dY, dX) pairs of ``wspmm``; ``out_dtype`` defaults to
+    dY's.  Padding columns of dX are written 0."""
+    n_src = rowptr_t.numel() - 1
+    nnz = col_t.numel()
+    ldo = ld_out or dY.shape[1]
+    if out is None:
+        out = torch.empty(n_src, ldo, dtype=out_dtype or dY.dtype, device=dY.device)
+    if checks.enabled():
+        checks.csr(rowptr_t, col_t, min(arg.shape[0], dY.shape[0]), "pool_bwd")
+        checks.rows(out, n_src, "pool_bwd out")
+        if eperm.numel() != nnz:
+            raise ValueError("CGNN_CHECK: pool_bwd: eperm has %d entries for %d edges" % (eperm.numel(), nnz))
+        checks.index(eperm, nnz, "pool_bwd eperm")
+        _check_arg(arg, 0, F, "pool_bwd")
+    if dY.is_cuda:
+        if arg.dtype != torch.int32 or eperm.dtype != torch.int32:
+            raise TypeError("pool_bwd: arg and eperm must be int32")
+        if not (dY.is_contiguous() and out.is_contiguous() and arg.is_contiguous()):
+            raise ValueError("pool_bwd: contiguous operands expected")
+        native.hip().gnn_pool_bwd(rowptr_t.data_ptr(), col_t.data_ptr(), eperm.data_ptr(), arg.data_ptr(),
+                                  arg.shape[1], dY.data_ptr(), dY.shape[1], out.data_ptr(), out.shape[1], n_src, F,
+                                  dtype_code(dY.dtype), dtype_code(out.dtype), _st(dY))
+        return out
+    at = _acc_dtype(dY.dtype)
+    rp = rowptr_t.long()
+    deg = rp[1:] - rp[:-1]
+    acc = torch.zeros(n_src, F, dtype=at)
+    for k in range(int(deg.max()) if n_src else 0):      # one chain per row, in transposed-edge order
+        r = torch.nonzero(deg > k).flatten()
+        t = rp[r] + k
+        i, e = col_t[t].long(), eperm[t].long()
+        acc[r] += torch.where(arg[i, :F].long() == e[:, None], dY[i, :F].to(at), torch.zeros((), dtype=at))
+    out[:n_src].zero_()
+    out[:n_src, :F] = acc.to(out.dtype)
     return out
 
 

@@ -2,6 +2,10 @@
 
 Layer:  h_i' = act( W_self h_i + W_neigh mean_{j in N(i)} h_j + b )
 
+``aggr="max"`` / ``"min"`` (``SAGE``, ``SAGETrainer``) replaces the mean by the element-wise
+max / min over the neighbours (``layers.pool_aggregate`` on gnn_pool.hip), on the autograd
+path only; the fused step implements the mean.
+
 Two training modes:
 
 * **full graph** -- every layer aggregates over the whole CSR (A + I) with the
@@ -45,6 +49,7 @@ from .. import native
 from ..utils.philox import model_key
 from . import ops
 from .data import GraphData
+from .layers import pool_aggregate
 from .linear import lin_bwd_data, lin_bwd_weight, lin_fwd
 
 
@@ -78,11 +83,19 @@ class Block:
         deg = (self.rowptr[1:] - self.rowptr[:-1]).float()
         self.inv_deg = torch.where(deg > 0, 1.0 / deg.clamp_min(1), torch.zeros_like(deg))
         self._t = None
+        self._tperm = None
 
     def transposed(self):
         if self._t is None:
             self._t = transpose_csr(self.rowptr, self.col, self.n_src)
         return self._t
+
+    def transposed_perm(self):
+        """``(rowptr_t, col_t, eperm)``: the transposed CSR with, per transposed edge, the
+        index of its forward edge (the max / min pooling backward).  Built once."""
+        if self._tperm is None:
+            self._tperm = transpose_csr(self.rowptr, self.col, self.n_src, with_perm=True)
+        return self._tperm
 
 
 class _MeanAggregate(torch.autograd.Function):
@@ -110,6 +123,9 @@ def mean_aggregate(h: torch.Tensor, block: Block) -> torch.Tensor:
     if h.shape[1] % 8:
         raise ValueError("feature width must be a multiple of 8 (pad the features)")
     return _MeanAggregate.apply(h, block)
+
+
+AGGREGATORS = ("mean", "max", "min")
 
 
 class _SageLinear(torch.autograd.Function):
@@ -147,8 +163,11 @@ class _SageLinear(torch.autograd.Function):
 
 class SAGE(torch.nn.Module):
     def __init__(self, in_dim: int, hidden: int, out_dim: int, layers: int = 2, dropout: float = 0.5,
-                 seed: int = 0):
+                 seed: int = 0, aggr: str = "mean"):
         super().__init__()
+        if aggr not in AGGREGATORS:
+            raise ValueError("aggr must be one of %s, got %r" % (AGGREGATORS, aggr))
+        self.aggr = aggr
         g = torch.Generator().manual_seed(seed)
         dims = [in_dim] + [hidden] * (layers - 1) + [out_dim]
         self.w_self = torch.nn.ParameterList()
@@ -162,7 +181,7 @@ class SAGE(torch.nn.Module):
         self.dropout = float(dropout)
 
     def layer(self, k: int, h: torch.Tensor, block: Block, last: bool):
-        agg = mean_aggregate(h, block)
+        agg = mean_aggregate(h, block) if self.aggr == "mean" else pool_aggregate(h, block, self.aggr)
         out = _SageLinear.apply(h[:block.n_dst], agg, self.w_self[k], self.w_neigh[k], self.bias[k])
         if not last:
             out = torch.relu(out)
@@ -350,8 +369,16 @@ class SAGETrainer:
     def __init__(self, g: GraphData, hidden: int = 256, layers: int = 2, dropout: float = 0.5,
                  lr: float = 0.003, fanouts: Optional[List[int]] = (15, 10), batch_size: int = 1024,
                  seed: int = 0, prefetch: bool = True, standardize: bool = True, bucket_mb: float = 16.0,
-                 sampler: Optional[str] = None, fused: Optional[bool] = None):
+                 sampler: Optional[str] = None, fused: Optional[bool] = None, aggr: str = "mean"):
         from ..parallel import dist as pdist
+        if aggr not in AGGREGATORS:
+            raise ValueError("aggr must be one of %s, got %r" % (AGGREGATORS, aggr))
+        if aggr != "mean":
+            if fused:
+                raise ValueError("the fused step implements the mean aggregator only; aggr=%r needs fused=False"
+                                 % (aggr,))
+            fused = False                     # the autograd path (SAGE.layer -> pool_aggregate)
+        self.aggr = aggr
         self.rank, self.world = pdist.rank(), pdist.world_size()
         self.g = g
         self.dev = g.rowptr.device
@@ -397,7 +424,7 @@ class SAGETrainer:
                 torch.distributed.broadcast(self._fused.params, 0)
             return
         # hidden width padded to a multiple of 8 (SpMM row alignment); output padded too
-        self.model = SAGE(F, hidden, self.C, layers, dropout, seed).to(self.dev)
+        self.model = SAGE(F, hidden, self.C, layers, dropout, seed, aggr=aggr).to(self.dev)
         self.model.w_self[0].data[g.n_features:] = 0
         self.model.w_neigh[0].data[g.n_features:] = 0
         self.opt = torch.optim.Adam(self.model.parameters(), lr=lr, fused=self.dev.type == "cuda")

@@ -55,12 +55,19 @@ class DeviceBlock:
             inv_deg = torch.where(deg > 0, 1.0 / deg.clamp_min(1), torch.zeros_like(deg))
         self.inv_deg = inv_deg
         self._t = transposed
+        self._tperm = None
 
     def transposed(self):
         if self._t is None:
             from .sage import transpose_csr
             self._t = transpose_csr(self.rowptr, self.col, self.n_src)
         return self._t
+
+    def transposed_perm(self):
+        if self._tperm is None:
+            from .sage import transpose_csr
+            self._tperm = transpose_csr(self.rowptr, self.col, self.n_src, with_perm=True)
+        return self._tperm
 
 
 class DeviceSampler:
