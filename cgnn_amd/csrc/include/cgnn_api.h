@@ -148,6 +148,17 @@ int gnn_launch_pool_bwd(const int* rowptr_t, const int* col_t, const int* eperm,
                         const void* dY, int lddy, void* dX, int lddx, int n_src, int F, int tdy, int tdx,
                         hipStream_t st);
 
+// ---- gnn_edge_softmax.hip: softmax over each row's edges and its gradient.  s / p / dp / ds
+// are fp32, head-major [K, ld] (head k's edge e at k * ld + e); p may alias s and ds may
+// alias dp.  lanes: the sub-group width, 0 = from nnz / n_rows.  -3: a required pointer
+// missing, K < 1, ld < nnz, or scale not a positive finite number; -1: a lanes value that
+// is not compiled; -4: the (rows x heads) grid would overflow; 0 without a launch for
+// n_rows <= 0 or nnz == 0
+int gnn_launch_edge_softmax_fwd(const int* rowptr, const float* s, float* p, int n_rows, int nnz, int K, long ld,
+                                float scale, int lanes, hipStream_t st);
+int gnn_launch_edge_softmax_bwd(const int* rowptr, const float* p, const float* dp, float* ds, int n_rows, int nnz,
+                                int K, long ld, float scale, int lanes, hipStream_t st);
+
 // ---- gnn_dense.hip: the fused two-layer dense GCN kernels.  The launchers return -1
 // when no compiled variant covers (F, HD, C); Python then raises
 int gnn_launch_dense_fwd(const void* AX, const float* W1, const float* b1, const float* W2, const float* dinv,

@@ -225,7 +225,22 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("rowptr_t"), py::arg("col_t"), py::arg("eperm"), py::arg("arg"), py::arg("ld_arg"), py::arg("dy"),
      py::arg("ld_dy"), py::arg("dx"), py::arg("ld_dx"), py::arg("n_src"), py::arg("F"), py::arg("dy_type"),
      py::arg("dx_type"), py::arg("st"));
-  m.def("gnn_spmm_fan", [](uint64_t rowptr, uint64_t col, uint64_t x, uint64_t y, uint64_t rscale, int n_rows, int F,
+  // softmax over each row's edges and its gradient (gnn_edge_softmax.hip)
+  m.def("gnn_edge_softmax_fwd", [](uint64_t rowptr, uint64_t s, uint64_t p, int n_rows, int nnz, int K, long ld,
+                                   float scale, int lanes, uint64_t st) {
+    chk(gnn_launch_edge_softmax_fwd(Pt<const int>(rowptr), Pt<const float>(s), Pt<float>(p), n_rows, nnz, K, ld,
+                                    scale, lanes, S(st)),
+        "gnn_edge_softmax_fwd");
+  }, py::arg("rowptr"), py::arg("s"), py::arg("p"), py::arg("n_rows"), py::arg("nnz"), py::arg("K"), py::arg("ld"),
+     py::arg("scale"), py::arg("lanes"), py::arg("st"));
+  m.def("gnn_edge_softmax_bwd", [](uint64_t rowptr, uint64_t p, uint64_t dp, uint64_t ds, int n_rows, int nnz, int K,
+                                   long ld, float scale, int lanes, uint64_t st) {
+    chk(gnn_launch_edge_softmax_bwd(Pt<const int>(rowptr), Pt<const float>(p), Pt<const float>(dp), Pt<float>(ds),
+                                    n_rows, nnz, K, ld, scale, lanes, S(st)),
+        "gnn_edge_softmax_bwd");
+  }, py::arg("rowptr"), py::arg("p"), py::arg("dp"), py::arg("ds"), py::arg("n_rows"), py::arg("nnz"), py::arg("K"),
+     py::arg("ld"), py::arg("scale"), py::arg("lanes"), py::arg("st"));
+  m.def("gnn_spmm_fan",[](uint64_t rowptr, uint64_t col, uint64_t x, uint64_t y, uint64_t rscale, int n_rows, int F,
                            int ldx, int ldy, long n_x_rows, long nnz, int max_deg, uint64_t st) {
     chk(gnn_launch_spmm_fan(Pt<const int>(rowptr), Pt<const int>(col), Pt<const void>(x), Pt<void>(y),
                             Pt<const float>(rscale), n_rows, F, ldx, ldy, n_x_rows, nnz, max_deg, S(st)),

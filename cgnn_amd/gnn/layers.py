@@ -15,6 +15,10 @@ track, not in the reference.
   and the edge values receive a gradient (``ops.sddmm``) when they require one.
 * ``pool_aggregate`` -- element-wise max / min over each node's neighbours
   (``ops.pool``), the gradient routed through the saved edge index (``ops.pool_bwd``).
+* ``edge_softmax`` / ``edge_dot`` / ``AttentionConv`` -- attention of any score form: a
+  softmax over each node's incoming edges (``ops.edge_softmax``), per-edge dot products
+  (``ops.sddmm``, differentiable through ``ops.wspmm``), and multi-head dot-product
+  attention built from them.
 
 Everything runs on the same ``ops.spmm`` as the fused 2-layer trainer (HIP on
 GPU tensors, PyTorch index ops on CPU tensors); dense products are hipBLASLt
@@ -262,6 +266,169 @@ def pool_aggregate(x: torch.Tensor, g, reduce: str = "max") -> torch.Tensor:
     element that supplied each result (the first edge on ties), through the saved edge index
     and a gather over the transposed CSR (``ops.pool_bwd``): deterministic, no atomics."""
     return _PoolAggregate.apply(x, g, reduce)
+
+
+def _pad_last(x: torch.Tensor, mult: int = 8) -> torch.Tensor:
+    F = x.shape[-1]
+    return x if F % mult == 0 else torch.nn.functional.pad(x, (0, mult - F % mult))
+
+
+class _EdgeSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, score, g, scale):
+        p = ops.edge_softmax(g.rowptr, score.contiguous(), scale=scale, nnz=g.col.numel())
+        ctx.g, ctx.scale = g, scale
+        ctx.save_for_backward(p)
+        return p
+
+    @staticmethod
+    def backward(ctx, dp):
+        p, = ctx.saved_tensors
+        ds = ops.edge_softmax_bwd(ctx.g.rowptr, p, dp.contiguous(), scale=ctx.scale, nnz=ctx.g.col.numel())
+        return ds, None, None
+
+
+def edge_softmax(score: torch.Tensor, g, scale: float = 1.0) -> torch.Tensor:
+    """Softmax of per-edge scores over each destination node's incoming edges
+    (``ops.edge_softmax``): ``score`` is ``[nnz]`` or head-major ``[K, nnz]`` in the edge order
+    of ``g`` (anything with ``rowptr`` and ``col``), the result has its shape; the scores are
+    multiplied by ``scale > 0`` first.  The backward runs ``ops.edge_softmax_bwd`` on the saved
+    output.  Deterministic, no atomics; fp32 on the GPU."""
+    return _EdgeSoftmax.apply(score, g, float(scale))
+
+
+def _n_rows(g) -> int:
+    return g.rowptr.numel() - 1
+
+
+class _EdgeDot(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, out, a, b, g):
+        F = a.shape[1]
+        ap, bp = pad_cols(a).contiguous(), pad_cols(b).contiguous()
+        if out is not None:
+            ctx.mark_dirty(out)
+        out = ops.sddmm(g.rowptr, g.col, ap, bp, F, out=out)
+        ctx.g, ctx.F = g, F
+        ctx.save_for_backward(ap, bp)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        ap, bp = ctx.saved_tensors
+        g, F = ctx.g, ctx.F
+        dout = dout.contiguous()
+        da = db = None
+        if ctx.needs_input_grad[1]:
+            da = ops.wspmm(g.rowptr, g.col, dout, bp, F)[:, :F]
+        if ctx.needs_input_grad[2]:
+            rp_t, col_t, eperm = g.transposed_perm()
+            db = ops.wspmm(rp_t, col_t, dout, ap, F, eperm=eperm)[:, :F]
+        # the overwritten buffer comes first (autograd takes input 0 of an in-place function
+        # for the tensor it changed); what it held before does not reach the result
+        return (torch.zeros_like(dout) if ctx.needs_input_grad[0] else None), da, db, None
+
+
+def edge_dot(a: torch.Tensor, b: torch.Tensor, g, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``out[e] = <a[i], b[j]>`` for every edge e = (i, j) of ``g`` (``ops.sddmm``), in fp32
+    (fp64 for fp64 inputs): ``a`` holds one row per destination, ``b`` one per source, in one
+    storage dtype.  ``out`` (optional, a contiguous ``[nnz]`` tensor, e.g. one head's row of a
+    ``[K, nnz]`` score buffer) is written in place and returned.  Differentiable in both
+    operands with no kernel of its own: ``da = wspmm(val=dout, X=b)`` over the forward CSR,
+    ``db = wspmm(val=dout, X=a, eperm=...)`` over ``g.transposed_perm()``."""
+    return _EdgeDot.apply(out, a, b, g)
+
+
+class _HeadsAggregate(torch.autograd.Function):
+    """``Y[k] = A_k V[k]`` for K heads: ``V`` is ``[K, n_src, D]`` (D a multiple of 8), ``alpha``
+    the head-major fp32 edge values ``[K, nnz]``, each head's slice read in place by
+    ``ops.wspmm``.  Backward: ``dV[k] = A_k^T dY[k]`` over the transposed CSR and
+    ``d alpha[k] = sddmm(dY[k], V[k])``, written into one ``[K, nnz]`` buffer."""
+
+    @staticmethod
+    def forward(ctx, V, alpha, g):
+        K, D = V.shape[0], V.shape[2]
+        Y = torch.empty(K, _n_rows(g), D, dtype=V.dtype, device=V.device)
+        for k in range(K):
+            ops.wspmm(g.rowptr, g.col, alpha[k], V[k], D, out=Y[k])
+        ctx.g = g
+        ctx.save_for_backward(V, alpha)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        V, alpha = ctx.saved_tensors
+        g = ctx.g
+        K, D = V.shape[0], V.shape[2]
+        dY = dY.contiguous()
+        dV = dalpha = None
+        if ctx.needs_input_grad[0]:
+            rp_t, col_t, eperm = g.transposed_perm()
+            dV = torch.empty_like(V)
+            for k in range(K):
+                ops.wspmm(rp_t, col_t, alpha[k], dY[k], D, eperm=eperm, out=dV[k])
+        if ctx.needs_input_grad[1]:
+            dalpha = torch.empty_like(alpha)
+            for k in range(K):
+                ops.sddmm(g.rowptr, g.col, dY[k], V[k], D, out=dalpha[k])
+        return dV, dalpha, None
+
+
+class AttentionConv(torch.nn.Module):
+    """Multi-head dot-product attention over a graph: PyG's ``TransformerConv`` without edge
+    features or gating.  With ``Q = h_dst Wq + bq``, ``K = h_src Wk + bk``, ``V = h_src Wv + bv``
+    projected as ``[heads, n, head_dim]`` (each head contiguous),
+
+        alpha^k_ij = softmax_j(<Q^k_i, K^k_j> / sqrt(head_dim))   over the edges (i, j) of g
+        out_i      = concat_k (or mean_k) sum_j alpha^k_ij V^k_j  (+ h_dst W_root) (+ bias)
+
+    The scores of all heads fill one fp32 ``[heads, nnz]`` buffer (``edge_dot`` per head) and
+    are normalised in one launch (``edge_softmax``); the aggregation and its gradient with
+    respect to alpha run on ``ops.wspmm`` / ``ops.sddmm``.  ``g``: anything ``pool_aggregate``
+    accepts; on a rectangular graph the destinations are the first rows of ``h``, as in
+    ``SAGE``.  Storage dtype follows the input; scores and alpha stay fp32.  Glorot-uniform
+    weights, zero biases."""
+
+    def __init__(self, in_dim: int, heads: int, head_dim: int, concat: bool = True, root_weight: bool = True,
+                 bias: bool = True, generator: Optional[torch.Generator] = None):
+        super().__init__()
+        self.in_dim, self.heads, self.head_dim, self.concat = in_dim, heads, head_dim, bool(concat)
+        self.out_dim = heads * head_dim if concat else head_dim
+
+        def glorot(fan_out, *shape):
+            bound = math.sqrt(6.0 / (in_dim + fan_out))
+            return torch.nn.Parameter((torch.rand(*shape, generator=generator) * 2 - 1) * bound)
+
+        hd = heads * head_dim
+        self.w_q = glorot(hd, heads, in_dim, head_dim)
+        self.w_k = glorot(hd, heads, in_dim, head_dim)
+        self.w_v = glorot(hd, heads, in_dim, head_dim)
+        self.b_q = torch.nn.Parameter(torch.zeros(heads, 1, head_dim))
+        self.b_k = torch.nn.Parameter(torch.zeros(heads, 1, head_dim))
+        self.b_v = torch.nn.Parameter(torch.zeros(heads, 1, head_dim))
+        self.w_root = glorot(self.out_dim, in_dim, self.out_dim) if root_weight else None
+        self.bias = torch.nn.Parameter(torch.zeros(self.out_dim)) if bias else None
+
+    def forward(self, h: torch.Tensor, g, return_attention: bool = False):
+        n, dt = _n_rows(g), h.dtype
+        n_src = getattr(g, "n_src", None) or n
+        if h.shape[0] < n_src:
+            raise ValueError("AttentionConv: %d feature rows for %d source nodes" % (h.shape[0], n_src))
+        h_src, h_dst = h[:n_src], h[:n]
+        q = _pad_last(torch.matmul(h_dst, self.w_q.to(dt)) + self.b_q.to(dt))
+        k = _pad_last(torch.matmul(h_src, self.w_k.to(dt)) + self.b_k.to(dt))
+        v = _pad_last(torch.matmul(h_src, self.w_v.to(dt)) + self.b_v.to(dt))
+        score = torch.empty(self.heads, g.col.numel(), dtype=ops._acc_dtype(dt), device=h.device)
+        for i in range(self.heads):                          # in place: score carries the history
+            edge_dot(q[i], k[i], g, out=score[i])
+        alpha = edge_softmax(score, g, scale=self.head_dim ** -0.5)
+        y = _HeadsAggregate.apply(v.contiguous(), alpha, g)[:, :, :self.head_dim]
+        out = y.permute(1, 0, 2).reshape(n, self.out_dim) if self.concat else y.mean(0)
+        if self.w_root is not None:
+            out = out + h_dst @ self.w_root.to(dt)
+        if self.bias is not None:
+            out = out + self.bias.to(dt)
+        return (out, alpha) if return_attention else out
 
 
 class _WeightedGCNLayer(torch.autograd.Function):

@@ -2,8 +2,8 @@
 
 The CPU branch is the numerical reference used by the tests (and lets the
 models run in CI); on a GPU the HIP kernels of csrc/kernels/gnn_sparse.hip (and
-gnn_wspmm.hip for the edge-weighted ops, gnn_pool.hip for max / min pooling) are
-mandatory -- a missing extension raises instead of silently falling back.
+gnn_wspmm.hip for the edge-weighted ops, gnn_pool.hip for max / min pooling,
+gnn_edge_softmax.hip for the softmax over a node's edges) are mandatory -- a missing extension raises instead of silently falling back.
 """
 from __future__ import annotations
 
@@ -335,6 +335,117 @@ def pool_bwd(rowptr_t, col_t, eperm, arg, dY, F, out=None, out_dtype=None, ld_ou
         acc[r] += torch.where(arg[i, :F].long() == e[:, None], dY[i, :F].to(at), torch.zeros((), dtype=at))
     out[:n_src].zero_()
     out[:n_src, :F] = acc.to(out.dtype)
+    return out
+
+
+_ES_LANES = (8, 16, 32, 64)
+
+
+def _edge_heads(t, what):
+    """(K, ld) of a head-major edge tensor: ``[nnz]`` is one head, ``[K, ld]`` K heads."""
+    if t.dim() == 1:
+        return 1, t.shape[0]
+    if t.dim() == 2:
+        return t.shape[0], t.shape[1]
+    raise ValueError("%s: [nnz] or [K, ld] expected, got shape %s" % (what, tuple(t.shape)))
+
+
+def _edge_softmax_args(rowptr, ts, names, scale, lanes, nnz, what):
+    """Shared validation of ``edge_softmax`` / ``edge_softmax_bwd``: (K, ld, nnz, lanes)."""
+    K, ld = _edge_heads(ts[0], what)
+    for t, name in zip(ts, names):
+        if t.shape != ts[0].shape or t.dtype != ts[0].dtype or t.device != ts[0].device:
+            raise ValueError("%s: %s must match %s in shape, dtype and device" % (what, name, names[0]))
+    nnz = ld if nnz is None else int(nnz)
+    lanes = 0 if lanes is None else int(lanes)
+    if checks.enabled():
+        if rowptr.dim() != 1 or rowptr.numel() < 1:
+            raise ValueError("CGNN_CHECK: %s: rowptr must be a non-empty vector" % what)
+        rp = rowptr.long()
+        if int(rp[0]) != 0 or bool((rp[1:] < rp[:-1]).any()):
+            raise ValueError("CGNN_CHECK: %s: rowptr must start at 0 and never decrease" % what)
+        if not int(rp[-1]) <= nnz <= ld:
+            raise ValueError("CGNN_CHECK: %s: rowptr ends at %d, nnz = %d, ld = %d" % (what, int(rp[-1]), nnz, ld))
+        if not (float(scale) > 0 and float(scale) < float("inf")):
+            raise ValueError("CGNN_CHECK: %s: scale must be positive and finite, got %r" % (what, scale))
+    if ts[0].is_cuda:
+        if ts[0].dtype != torch.float32:
+            raise TypeError("%s: scores are fp32 on the GPU, got %s" % (what, ts[0].dtype))
+        if rowptr.dtype != torch.int32:
+            raise TypeError("%s: rowptr must be int32" % what)
+        if not all(t.is_contiguous() for t in ts):
+            raise ValueError("%s: contiguous operands expected" % what)
+    return K, ld, nnz, lanes
+
+
+def _segments(rowptr, t, K, ld):
+    """CPU branch: (row id per edge, the [K, E] view of the edges the CSR names)."""
+    rows = _row_ids(rowptr)
+    return rows, t.reshape(K, ld)[:, :rows.numel()]
+
+
+def edge_softmax(rowptr, score, scale=1.0, out=None, lanes=None, nnz=None):
+    """Softmax over each row's edges (gnn_edge_softmax.hip, edge_softmax_fwd_kernel):
+    ``p[k,e] = exp(scale (s[k,e] - m)) / sum_e' exp(scale (s[k,e'] - m))`` over the edges of
+    row i, ``m`` their maximum, ``scale > 0``.  ``score`` is ``[nnz]`` or head-major ``[K, ld]``
+    (``ld >= nnz``: one head is a contiguous slice that ``sddmm(out=...)`` writes and
+    ``wspmm(val=...)`` reads in place); fp32 on the GPU.  ``out`` (same shape; default a new
+    tensor) may be ``score`` itself; nothing outside the first ``rowptr[-1]`` elements of a
+    head is written.  An empty row writes nothing, a single edge gives exactly 1, a ``-inf``
+    score exactly 0, a row of ``-inf`` all 0; a NaN or ``+inf`` score makes its (row, head)
+    NaN and nothing else.  No atomics: bit-identical from run to run, and a row's result
+    does not depend on where it stands.  ``lanes``: force the sub-group width (8 / 16 / 32
+    / 64; default: chosen from ``nnz / n_rows``); ``nnz``: the number of edges when ``ld``
+    exceeds it (default ``ld``; only that choice looks at it).  CPU tensors: PyTorch in fp32,
+    or fp64 for fp64 inputs."""
+    if out is None:
+        out = torch.empty_like(score)
+    K, ld, nnz, lanes = _edge_softmax_args(rowptr, (score, out), ("score", "out"), scale, lanes, nnz, "edge_softmax")
+    n = rowptr.numel() - 1
+    if score.is_cuda:
+        native.hip().gnn_edge_softmax_fwd(rowptr.data_ptr(), score.data_ptr(), out.data_ptr(), n, nnz, K, ld,
+                                          float(scale), lanes, _st(score))
+        return out
+    if lanes not in (0,) + _ES_LANES:
+        raise ValueError("edge_softmax: lanes must be one of %s, got %d" % (_ES_LANES, lanes))
+    at = _acc_dtype(score.dtype)
+    rows, s = _segments(rowptr, score, K, ld)
+    if rows.numel() == 0:
+        return out
+    s = s.to(at)
+    m = torch.full((K, n), float("-inf"), dtype=at).scatter_reduce_(1, rows.expand(K, -1), s, "amax")
+    m = torch.where(m == float("-inf"), torch.zeros_like(m), m)
+    ex = torch.exp(scale * (s - m[:, rows]))
+    l = torch.zeros(K, n, dtype=at).index_add_(1, rows, ex)
+    rinv = torch.where(l == 0, torch.zeros_like(l), 1.0 / l)           # a NaN sum stays NaN
+    out.view(K, ld)[:, :rows.numel()] = (ex * rinv[:, rows]).to(out.dtype)
+    return out
+
+
+def edge_softmax_bwd(rowptr, p, dp, scale=1.0, out=None, lanes=None, nnz=None):
+    """The gradient of ``edge_softmax`` from its saved output (gnn_edge_softmax.hip,
+    edge_softmax_bwd_kernel): ``ds[k,e] = scale p[k,e] (dp[k,e] - sum_e' p[k,e'] dp[k,e'])``.
+    ``p``, ``dp`` and ``out`` share one shape (``[nnz]`` or ``[K, ld]``); ``out`` may be ``dp``
+    itself (not ``p``).  Layout, ``lanes``, ``nnz``, determinism and the CPU branch as in
+    ``edge_softmax``."""
+    if out is None:
+        out = torch.empty_like(dp)
+    K, ld, nnz, lanes = _edge_softmax_args(rowptr, (p, dp, out), ("p", "dp", "out"), scale, lanes, nnz,
+                                           "edge_softmax_bwd")
+    n = rowptr.numel() - 1
+    if p.is_cuda:
+        native.hip().gnn_edge_softmax_bwd(rowptr.data_ptr(), p.data_ptr(), dp.data_ptr(), out.data_ptr(), n, nnz, K,
+                                          ld, float(scale), lanes, _st(p))
+        return out
+    if lanes not in (0,) + _ES_LANES:
+        raise ValueError("edge_softmax_bwd: lanes must be one of %s, got %d" % (_ES_LANES, lanes))
+    at = _acc_dtype(p.dtype)
+    rows, pv = _segments(rowptr, p, K, ld)
+    if rows.numel() == 0:
+        return out
+    pv, g = pv.to(at), dp.reshape(K, ld)[:, :rows.numel()].to(at)
+    dot = torch.zeros(K, n, dtype=at).index_add_(1, rows, pv * g)
+    out.view(K, ld)[:, :rows.numel()] = (scale * pv * (g - dot[:, rows])).to(out.dtype)
     return out
 
 
