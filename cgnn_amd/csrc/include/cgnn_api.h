@@ -139,6 +139,18 @@ int gnn_launch_wspmm(const int* rowptr, const int* col, const float* val, const 
 int gnn_launch_sddmm(const int* rowptr, const int* col, const void* A, const void* B, float* out, const float* rscale,
                      const float* cscale, int n_rows, int F, int lda, int ldb, int t, hipStream_t st);
 
+// ---- gnn_espmm.hip: the aggregate with a feature row per edge, and its gradient with
+// respect to the edge rows (dE) and the edge values (dval).  X, E, Y, dY, dE share the
+// storage type t; val / dval are fp32; op: 0 add, 1 mul; X may be null (the sum of edge
+// rows), val and eperm too; dE or dval may be null, not both.  -3: a bad stride, E or an
+// output missing, relu with op = 1; -5: t outside 0..2; -1: an op that is not compiled
+int gnn_launch_espmm(const int* rowptr, const int* col, const float* val, const int* eperm, const void* X,
+                     const void* E, void* Y, int n_rows, int F, int ldx, int lde, int ldy, int t, int op, int relu,
+                     hipStream_t st);
+int gnn_launch_egrad(const int* rowptr, const int* col, const float* val, const void* dY, const void* X,
+                     const void* E, void* dE, float* dval, int n_rows, int F, int lddy, int ldx, int lde, int ldde,
+                     int t, int op, int relu, hipStream_t st);
+
 // ---- gnn_pool.hip: max / min neighbour pooling with the arg edge index, and its gradient
 // over the transposed CSR.  t / tdy / tdx: storage types; arg may be null in the forward;
 // -3 for a bad stride or a missing pointer, -5 for a type (pair) that is not compiled

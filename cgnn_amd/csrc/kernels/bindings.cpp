@@ -207,6 +207,27 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("rowptr"), py::arg("col"), py::arg("a"), py::arg("b"), py::arg("out"), py::arg("rscale"),
      py::arg("cscale"), py::arg("n_rows"), py::arg("F"), py::arg("ld_a"), py::arg("ld_b"), py::arg("type"),
      py::arg("st"));
+  // the aggregate with a feature row per edge and its edge gradients (gnn_espmm.hip)
+  m.def("gnn_espmm", [](uint64_t rowptr, uint64_t col, uint64_t val, uint64_t eperm, uint64_t x, uint64_t e,
+                        uint64_t y, int n_rows, int F, int ld_x, int ld_e, int ld_y, int type, int op, int relu,
+                        uint64_t st) {
+    chk(gnn_launch_espmm(Pt<const int>(rowptr), Pt<const int>(col), Pt<const float>(val), Pt<const int>(eperm),
+                         Pt<const void>(x), Pt<const void>(e), Pt<void>(y), n_rows, F, ld_x, ld_e, ld_y, type, op,
+                         relu, S(st)),
+        "gnn_espmm");
+  }, py::arg("rowptr"), py::arg("col"), py::arg("val"), py::arg("eperm"), py::arg("x"), py::arg("e"), py::arg("y"),
+     py::arg("n_rows"), py::arg("F"), py::arg("ld_x"), py::arg("ld_e"), py::arg("ld_y"), py::arg("type"),
+     py::arg("op"), py::arg("relu"), py::arg("st"));
+  m.def("gnn_egrad", [](uint64_t rowptr, uint64_t col, uint64_t val, uint64_t dy, uint64_t x, uint64_t e,
+                        uint64_t de, uint64_t dval, int n_rows, int F, int ld_dy, int ld_x, int ld_e, int ld_de,
+                        int type, int op, int relu, uint64_t st) {
+    chk(gnn_launch_egrad(Pt<const int>(rowptr), Pt<const int>(col), Pt<const float>(val), Pt<const void>(dy),
+                         Pt<const void>(x), Pt<const void>(e), Pt<void>(de), Pt<float>(dval), n_rows, F, ld_dy,
+                         ld_x, ld_e, ld_de, type, op, relu, S(st)),
+        "gnn_egrad");
+  }, py::arg("rowptr"), py::arg("col"), py::arg("val"), py::arg("dy"), py::arg("x"), py::arg("e"), py::arg("de"),
+     py::arg("dval"), py::arg("n_rows"), py::arg("F"), py::arg("ld_dy"), py::arg("ld_x"), py::arg("ld_e"),
+     py::arg("ld_de"), py::arg("type"), py::arg("op"), py::arg("relu"), py::arg("st"));
   // max / min neighbour pooling and its gradient (gnn_pool.hip)
   m.def("gnn_pool_fwd", [](uint64_t rowptr, uint64_t col, uint64_t x, uint64_t y, uint64_t arg, int n_rows, int F,
                            int ld_x, int ld_y, int ld_arg, int type, int is_min, uint64_t st) {

@@ -19,6 +19,10 @@ track, not in the reference.
   softmax over each node's incoming edges (``ops.edge_softmax``), per-edge dot products
   (``ops.sddmm``, differentiable through ``ops.wspmm``), and multi-head dot-product
   attention built from them.
+* ``edge_aggregate`` / ``GINEConv`` / ``CFConv`` -- message passing with a feature row per
+  edge (``ops.espmm``): ``sum_j relu(x_j + e_ij)`` or ``sum_j x_j * e_ij``, differentiable in
+  the node rows, the edge rows (``ops.egrad``) and optional per-edge weights; GIN with edge
+  features and SchNet's continuous-filter convolution built on it.
 
 Everything runs on the same ``ops.spmm`` as the fused 2-layer trainer (HIP on
 GPU tensors, PyTorch index ops on CPU tensors); dense products are hipBLASLt
@@ -429,6 +433,151 @@ class AttentionConv(torch.nn.Module):
         if self.bias is not None:
             out = out + self.bias.to(dt)
         return (out, alpha) if return_attention else out
+
+
+class _EdgeAggregate(torch.autograd.Function):
+    """``ops.espmm`` with its three gradients: ``de`` / ``dval`` from one ``ops.egrad`` call
+    (only what is asked for), ``dx`` from ``ops.espmm`` over the transposed CSR."""
+
+    @staticmethod
+    def forward(ctx, x, e, val, g, op, relu):
+        F = e.shape[1]
+        ep = pad_cols(e).contiguous()
+        xp = pad_cols(x).contiguous() if x is not None else None
+        vc = val.detach().to(ops._acc_dtype(e.dtype)).contiguous() if val is not None else None
+        y = ops.espmm(g.rowptr, g.col, xp, ep, F, op=op, relu=relu, val=vc)
+        ctx.g, ctx.F, ctx.op, ctx.relu = g, F, op, relu
+        ctx.val_dtype = val.dtype if val is not None else None
+        ctx.save_for_backward(xp, ep, vc)
+        return y[:, :F] if y.shape[1] != F else y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xp, ep, vc = ctx.saved_tensors
+        g, F, op, relu = ctx.g, ctx.F, ctx.op, ctx.relu
+        need_x, need_e, need_v = ctx.needs_input_grad[:3]
+        dyp = pad_cols(gy).contiguous()
+        # op="add": dx is the sum of the dE rows, which are then computed (into a scratch
+        # buffer) even when e needs no gradient
+        want_de = need_e or (need_x and op == "add")
+        dE = dval = dx = None
+        if want_de or need_v:
+            dE, dval = ops.egrad(g.rowptr, g.col, dyp, xp, ep, F, op=op, relu=relu, val=vc, want_dE=want_de,
+                                 want_dval=need_v)
+        if need_x:
+            rp_t, col_t, eperm = g.transposed_perm()
+            if op == "mul":
+                dx = ops.espmm(rp_t, col_t, dyp, ep, F, op="mul", val=vc, eperm=eperm)
+            else:                                    # the ReLU mask and w_e are already in dE
+                dx = ops.espmm(rp_t, col_t, None, dE, F, eperm=eperm)
+            if dx.shape[0] < xp.shape[0]:            # rows of x beyond the graph's sources
+                dx = torch.cat([dx, dx.new_zeros(xp.shape[0] - dx.shape[0], dx.shape[1])])
+            dx = dx[:, :F] if dx.shape[1] != F else dx
+        de = (dE[:, :F] if dE.shape[1] != F else dE) if need_e else None
+        return dx, de, (dval.to(ctx.val_dtype) if need_v else None), None, None, None
+
+
+def edge_aggregate(x: Optional[torch.Tensor], e: torch.Tensor, g, op: str = "add", relu: bool = False,
+                   val: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Message passing with a feature row per edge (``ops.espmm``): ``y_i = sum_j w_ij m_ij``
+    over the edges (i, j) of ``g`` with ``m_ij = x_j + e_ij`` (``op="add"``; through a ReLU with
+    ``relu=True``) or ``m_ij = x_j * e_ij`` (``op="mul"``).  ``e`` is ``[nnz, F]`` in the edge
+    order of ``g``, ``x`` is ``[n_src, F]`` in the same storage dtype; ``x=None`` sums the edge
+    rows into their destinations.  ``val`` (optional, ``[nnz]``, fp32): the weights ``w_ij``,
+    default 1.  ``g``: anything ``pool_aggregate`` accepts.  Differentiable in ``x``, ``e`` and
+    ``val``: ``de`` and ``dval`` come from one ``ops.egrad`` call that computes only what is
+    required; ``dx`` is ``ops.espmm`` over ``g.transposed_perm()`` -- for ``"mul"`` of the
+    incoming gradient times ``e``, for ``"add"`` the sum of the ``de`` rows (which carry the
+    ReLU mask and ``w_ij``).  In bf16 / fp16 those rows are rounded to the storage type
+    before they are summed.  Deterministic, no atomics."""
+    return _EdgeAggregate.apply(x, e, val, g, op, bool(relu))
+
+
+class _Dense(torch.nn.Module):
+    """``x W (+ b)``: Glorot-uniform ``W`` ``[in_dim, out_dim]``, zero ``b``; the parameters
+    are cast to the input's dtype."""
+
+    def __init__(self, in_dim: int, out_dim: int, bias: bool = True, generator: Optional[torch.Generator] = None):
+        super().__init__()
+        bound = math.sqrt(6.0 / (in_dim + out_dim))
+        self.weight = torch.nn.Parameter((torch.rand(in_dim, out_dim, generator=generator) * 2 - 1) * bound)
+        self.bias = torch.nn.Parameter(torch.zeros(out_dim)) if bias else None
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        y = x @ self.weight.to(x.dtype)
+        return y + self.bias.to(x.dtype) if self.bias is not None else y
+
+
+def _src_dst(h, g, what):
+    n = _n_rows(g)
+    n_src = getattr(g, "n_src", None) or n
+    if h.shape[0] < max(n_src, n):
+        raise ValueError("%s: %d feature rows for %d source and %d destination nodes" % (what, h.shape[0], n_src, n))
+    return h[:n_src], h[:n]
+
+
+class GINEConv(torch.nn.Module):
+    """GIN with edge features (PyG's ``GINEConv``):
+
+        out_i = nn((1 + eps) x_i + sum_j relu(x_j + lin(e_ij)))   over the edges (i, j) of g
+
+    ``nn`` is any module mapping ``[n, in_dim]`` rows; ``lin``, a ``Linear(edge_dim, in_dim)``
+    (Glorot-uniform weight, zero bias), exists only when ``edge_dim`` is given -- otherwise the
+    edge rows must already have the width of ``x``.  ``eps`` is a parameter with
+    ``train_eps=True``.  The sum runs on ``edge_aggregate`` (``ops.espmm``, add + ReLU).  ``g``:
+    anything ``pool_aggregate`` accepts; on a rectangular graph the destinations are the first
+    rows of ``x``, as in ``SAGE``."""
+
+    def __init__(self, nn: torch.nn.Module, eps: float = 0.0, train_eps: bool = False, in_dim: Optional[int] = None,
+                 edge_dim: Optional[int] = None, generator: Optional[torch.Generator] = None):
+        super().__init__()
+        self.nn = nn
+        if train_eps:
+            self.eps = torch.nn.Parameter(torch.tensor([float(eps)]))
+        else:
+            self.register_buffer("eps", torch.tensor([float(eps)]))
+        if edge_dim is not None:
+            if in_dim is None:
+                raise ValueError("GINEConv: edge_dim needs in_dim (the width of x)")
+            self.lin = _Dense(edge_dim, in_dim, generator=generator)
+        else:
+            self.lin = None
+
+    def forward(self, x: torch.Tensor, g, e: torch.Tensor) -> torch.Tensor:
+        x_src, x_dst = _src_dst(x, g, "GINEConv")
+        if self.lin is not None:
+            e = self.lin(e)
+        if e.shape[1] != x.shape[1]:
+            raise ValueError("GINEConv: edge rows of width %d for node rows of width %d (pass edge_dim)"
+                             % (e.shape[1], x.shape[1]))
+        agg = edge_aggregate(x_src, e, g, "add", relu=True)
+        return self.nn((1 + self.eps.to(x.dtype)) * x_dst + agg)
+
+
+class CFConv(torch.nn.Module):
+    """SchNet's continuous-filter convolution:
+
+        h = x W1,   W_ij = Linear(ssp(Linear(e_ij))),   out_i = Linear(sum_j c_ij h_j * W_ij)
+
+    with ``ssp(z) = softplus(z) - log 2``, ``W1`` ``[in_dim, n_filters]`` without bias, the filter
+    network ``edge_dim -> n_filters -> n_filters`` and the output layer ``n_filters -> out_dim``.
+    ``cutoff`` (optional, ``[nnz]``): the per-edge weights ``c_ij`` (e.g. a cosine cutoff of the
+    distance), differentiable.  The sum runs on ``edge_aggregate`` (``ops.espmm``, mul).
+    Glorot-uniform weights, zero biases.  ``g``: anything ``pool_aggregate`` accepts."""
+
+    def __init__(self, in_dim: int, out_dim: int, n_filters: int, edge_dim: int,
+                 generator: Optional[torch.Generator] = None):
+        super().__init__()
+        self.lin1 = _Dense(in_dim, n_filters, bias=False, generator=generator)
+        self.filter1 = _Dense(edge_dim, n_filters, generator=generator)
+        self.filter2 = _Dense(n_filters, n_filters, generator=generator)
+        self.lin2 = _Dense(n_filters, out_dim, generator=generator)
+
+    def forward(self, x: torch.Tensor, g, e: torch.Tensor, cutoff: Optional[torch.Tensor] = None) -> torch.Tensor:
+        x_src, _ = _src_dst(x, g, "CFConv")
+        h = self.lin1(x_src)
+        w = self.filter2(torch.nn.functional.softplus(self.filter1(e)) - math.log(2.0))
+        return self.lin2(edge_aggregate(h, w, g, "mul", val=cutoff))
 
 
 class _WeightedGCNLayer(torch.autograd.Function):

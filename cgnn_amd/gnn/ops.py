@@ -3,7 +3,8 @@
 The CPU branch is the numerical reference used by the tests (and lets the
 models run in CI); on a GPU the HIP kernels of csrc/kernels/gnn_sparse.hip (and
 gnn_wspmm.hip for the edge-weighted ops, gnn_pool.hip for max / min pooling,
-gnn_edge_softmax.hip for the softmax over a node's edges) are mandatory -- a missing extension raises instead of silently falling back.
+gnn_edge_softmax.hip for the softmax over a node's edges, gnn_espmm.hip for the aggregate
+with a feature row per edge) are mandatory -- a missing extension raises instead of silently falling back.
 """
 from __future__ import annotations
 
@@ -220,6 +221,141 @@ def sddmm(rowptr, col, A, B, F, rscale=None, cscale=None, out=None):
         d = d * cscale[j].to(at)
     out[:nnz] = d.to(out.dtype)
     return out
+
+
+_EDGE_OPS = {"add": 0, "mul": 1}
+
+
+def _edge_args(what, rowptr, col, X, E, op, relu, val, eperm, others):
+    """Shared validation of ``espmm`` / ``egrad``: the op code, after the type and layout
+    checks that hold on every device (``others``: further (name, tensor) operands sharing
+    E's storage type)."""
+    if op not in _EDGE_OPS:
+        raise ValueError("%s: op must be 'add' or 'mul', got %r" % (what, op))
+    if relu and op == "mul":
+        raise ValueError("%s: relu goes with op='add' only" % what)
+    for name, t in (("X", X),) + tuple(others):
+        if t is not None and t.dtype != E.dtype:
+            raise TypeError("%s: %s and E must share a dtype, got %s and %s" % (what, name, t.dtype, E.dtype))
+    if val is not None and val.dtype != _acc_dtype(E.dtype):
+        raise TypeError("%s: edge values must be %s, got %s" % (what, _acc_dtype(E.dtype), val.dtype))
+    if eperm is not None and eperm.dtype != torch.int32:
+        raise TypeError("%s: eperm must be int32" % what)
+    for name, t in (("X", X), ("E", E), ("val", val), ("eperm", eperm)) + tuple(others):
+        if t is not None and not t.is_contiguous():
+            raise ValueError("%s: contiguous operands expected (%s)" % (what, name))
+    if checks.enabled():
+        nnz = col.numel()
+        checks.csr(rowptr, col, X.shape[0] if X is not None else 1 << 62, what)
+        if eperm is None:
+            checks.rows(E, nnz, what + " E")
+            checks.rows(val, nnz, what + " val")
+        else:
+            if eperm.numel() != nnz:
+                raise ValueError("CGNN_CHECK: %s: eperm has %d entries for %d edges" % (what, eperm.numel(), nnz))
+            checks.index(eperm, E.shape[0] if val is None else min(E.shape[0], val.numel()), what + " eperm")
+    return _EDGE_OPS[op]
+
+
+def _edge_messages(col, X, E, F, op, relu, eperm, nnz, at):
+    """m_e of ``espmm`` / ``egrad`` and the edge-row index p(e), in PyTorch index ops."""
+    pe = eperm.long() if eperm is not None else torch.arange(nnz, device=E.device)
+    m = E[pe, :F].to(at)
+    if X is not None:
+        x = X[col.long(), :F].to(at)
+        m = x * m if op == "mul" else x + m
+        if relu:
+            m = m.clamp_min(0)
+    return m, pe
+
+
+def espmm(rowptr, col, X, E, F, op="add", relu=False, val=None, eperm=None, out=None, ld_out=None):
+    """Y[i,:F] = sum_{e in row i} w_e * m_e: the CSR aggregate with a feature row per edge
+    (gnn_espmm.hip, espmm_kernel).  ``E`` is ``[n_edge_rows, lde]``; ``p(e) = eperm[e]`` with
+    an edge permutation (int32 [nnz], e.g. the transposed CSR's map to the forward edges),
+    else ``e``; ``w_e = val[p(e)]`` (fp32, default 1).  ``op="add"``: ``m_e = X[col[e]] +
+    E[p(e)]``, through ``max(., 0)`` with ``relu``; ``op="mul"``: ``m_e = X[col[e]] * E[p(e)]``;
+    ``X=None``: ``m_e = E[p(e)]``, the sum of edge rows into their destinations.  X, E and Y
+    share one storage type (fp32 / bf16 / fp16 on the GPU).  Padding columns of Y are
+    written 0.  Per row and feature the sum is one fmaf chain in edge order whatever the
+    launch: bit-identical from run to run, no atomics.  CPU tensors: PyTorch, fp32
+    accumulation (fp64 for fp64 inputs)."""
+    n = rowptr.numel() - 1
+    nnz = col.numel()
+    if out is None:
+        out = torch.empty(n, ld_out or E.shape[1], dtype=E.dtype, device=E.device)
+    code = _edge_args("espmm", rowptr, col, X, E, op, relu, val, eperm, (("out", out),))
+    if checks.enabled():
+        checks.rows(out, n, "espmm out")
+    if E.is_cuda:
+        if n == 0:
+            return out
+        if E.shape[0] == 0 and nnz:
+            raise ValueError("espmm: E has no rows for %d edges" % nnz)
+        # a graph without edges: the launcher wants an E, and an empty tensor's pointer is
+        # null; no row has an edge, so the placeholder is never read
+        e_ptr = E.data_ptr() if E.shape[0] else _nonempty_ids(col).data_ptr()
+        native.hip().gnn_espmm(rowptr.data_ptr(), col.data_ptr(), _ptr(val), _ptr(eperm), _ptr(X), e_ptr,
+                               out.data_ptr(), n, F, X.shape[1] if X is not None else 0, E.shape[1], out.shape[1],
+                               dtype_code(E.dtype), code, int(bool(relu)), _st(E))
+        return out
+    at = _acc_dtype(E.dtype)
+    m, pe = _edge_messages(col, X, E, F, op, relu, eperm, nnz, at)
+    if val is not None:
+        m = m * val[pe].to(at)[:, None]
+    acc = torch.zeros(n, F, dtype=at).index_add_(0, _row_ids(rowptr), m)
+    out[:n].zero_()
+    out[:n, :F] = acc.to(out.dtype)
+    return out
+
+
+def egrad(rowptr, col, dY, X, E, F, op="add", relu=False, val=None, dE=None, dval=None, want_dE=True,
+          want_dval=False):
+    """The gradient of ``espmm`` (forward CSR, no edge permutation) with respect to the edge
+    rows and the edge values (gnn_espmm.hip, egrad_kernel): for every edge e = (i, j),
+    ``dE[e,:F] = w_e * dY[i,:F] * d`` with ``d = 1`` (add), ``1[X[j] + E[e] > 0]`` (add with
+    ``relu``: 0 where the sum is 0, as ``torch.relu``), ``X[j]`` (mul), and ``dval[e] =
+    <dY[i], m_e>`` (m_e as in the forward, after the ReLU).  Returns ``(dE, dval)``; an output
+    that is neither passed in nor wanted is None and not computed.  ``dE`` has E's storage
+    type and row stride (padding columns written 0), ``dval`` is fp32 [nnz] (fp64 for fp64
+    inputs on the CPU).  Fixed-order sums, no atomics: bit-identical from run to run."""
+    n = rowptr.numel() - 1
+    nnz = col.numel()
+    if dE is None and want_dE:
+        dE = torch.empty(nnz, E.shape[1], dtype=E.dtype, device=E.device)
+    if dval is None and want_dval:
+        dval = torch.empty(nnz, dtype=_acc_dtype(E.dtype), device=E.device)
+    if dE is None and dval is None:
+        raise ValueError("egrad: neither dE nor dval requested")
+    code = _edge_args("egrad", rowptr, col, X, E, op, relu, val, None, (("dY", dY), ("dE", dE)))
+    if dval is not None and (dval.dtype != _acc_dtype(E.dtype) or not dval.is_contiguous()):
+        raise TypeError("egrad: dval must be a contiguous %s vector, got %s" % (_acc_dtype(E.dtype), dval.dtype))
+    if checks.enabled():
+        checks.rows(dY, n, "egrad dY")
+        checks.rows(dE, nnz, "egrad dE")
+        checks.rows(dval, nnz, "egrad dval")
+    if E.is_cuda:
+        if nnz == 0:                                     # no edge: nothing to write
+            return dE, dval
+        native.hip().gnn_egrad(rowptr.data_ptr(), col.data_ptr(), _ptr(val), dY.data_ptr(), _ptr(X), E.data_ptr(),
+                               _ptr(dE), _ptr(dval), n, F, dY.shape[1], X.shape[1] if X is not None else 0,
+                               E.shape[1], dE.shape[1] if dE is not None else 0, dtype_code(E.dtype), code,
+                               int(bool(relu)), _st(E))
+        return dE, dval
+    at = _acc_dtype(E.dtype)
+    g = dY[_row_ids(rowptr), :F].to(at)
+    if dval is not None:
+        m, _ = _edge_messages(col, X, E, F, op, relu, None, nnz, at)
+        dval[:nnz] = (g * m).sum(1).to(dval.dtype)
+    if dE is not None:
+        d = g if val is None else g * val[:nnz].to(at)[:, None]
+        if X is not None and op == "mul":
+            d = d * X[col.long(), :F].to(at)
+        elif X is not None and relu:
+            d = d * (X[col.long(), :F].to(at) + E[:nnz, :F].to(at) > 0).to(at)
+        dE[:nnz].zero_()
+        dE[:nnz, :F] = d.to(dE.dtype)
+    return dE, dval
 
 
 def _pool_reduce(reduce) -> bool:
