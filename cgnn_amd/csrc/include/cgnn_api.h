@@ -191,6 +191,19 @@ int gnn_launch_fused_bwd(const void* AX, const void* dY2, const float* W1, const
 // ---- gnn_linear.hip: generic fused dense layers.  The launchers return the code to
 // Python: 0 ok, -1 no variant, -3 bad shape, -4 row ids / scales do not fit
 int gnn_lin_fwd_kc_wanted(int K, int N, int ldy);
+// Read-only queries (host only): the kernel a launcher selects for a call of that shape, by
+// the selection function the launcher itself dispatches on.  Negative: the launcher's
+// error code; else family * 1000000 + a * 1000 + b with family 1 lin_ws (a = KS, b = NW),
+// 2 the slab kernel (a = KS / KN, b = 10 * waves per block + staged stores), 3 lin_fwd_kc
+// (a = FG), 4 lin_gemm, 5 lin_bwd_weight2 (a = KT, b = 10 * NB + HAS_YM), 6 lin_bwd_weight
+// (a = KT).  gnn_lin_ws_grid: blocks of lin_ws<KS, NW> for n rows (-1: not compiled).
+int gnn_lin_fwd_variant(int ld1, int K1, int has_x2, int ld2, int K2, int N, int ldy, int n, float p, int has_idx1,
+                        int has_rscale, int has_tail, int nsplit, int tk, int et);
+int gnn_lin_bwd_data_variant(int lddy, int has_ym, int ldym, int N, int K1, int has_dx2, int K2, int ldx1, int ldx2,
+                             int n, int has_rscale, int dx1_f32);
+int gnn_lin_bwd_weight_variant(int ld1, int K1, int has_x2, int ld2, int K2, int lddy, int has_ym, int ldym, int N,
+                               int n, int has_idx1);
+int gnn_lin_ws_grid(int ks, int nw, int et, int bwd, int n);
 int gnn_launch_lin_fwd(const void* x1, int ld1, int K1, const void* x2, int ld2, int K2, const float* W, int N,
                        const float* bias, void* Y, int ldy, int n, int relu, float p, uint32_t k0, uint32_t k1,
                        uint32_t step, uint32_t row0, const int* stepp, const float* rscale, const int* idx1,

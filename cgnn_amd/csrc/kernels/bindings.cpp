@@ -521,6 +521,19 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("tk") = 1, py::arg("et") = 0);
   m.def("gnn_lin_fwd_image_bytes", &gnn_lin_fwd_image_bytes);
   m.def("gnn_lin_fwd_kc_wanted", &gnn_lin_fwd_kc_wanted);
+  // which kernel a launcher selects for a shape (read-only; encoding in cgnn_api.h)
+  m.def("gnn_lin_fwd_variant", &gnn_lin_fwd_variant, py::arg("ld1"), py::arg("K1"), py::arg("has_x2"), py::arg("ld2"),
+        py::arg("K2"), py::arg("N"), py::arg("ldy"), py::arg("n"), py::arg("p") = 0.f, py::arg("has_idx1") = 0,
+        py::arg("has_rscale") = 0, py::arg("has_tail") = 0, py::arg("nsplit") = 0, py::arg("tk") = 1,
+        py::arg("et") = 0);
+  m.def("gnn_lin_bwd_data_variant", &gnn_lin_bwd_data_variant, py::arg("lddy"), py::arg("has_ym"), py::arg("ldym"),
+        py::arg("N"), py::arg("K1"), py::arg("has_dx2"), py::arg("K2"), py::arg("ldx1"), py::arg("ldx2"), py::arg("n"),
+        py::arg("has_rscale") = 0, py::arg("dx1_f32") = 0);
+  m.def("gnn_lin_bwd_weight_variant", &gnn_lin_bwd_weight_variant, py::arg("ld1"), py::arg("K1"), py::arg("has_x2"),
+        py::arg("ld2"), py::arg("K2"), py::arg("lddy"), py::arg("has_ym"), py::arg("ldym"), py::arg("N"), py::arg("n"),
+        py::arg("has_idx1") = 0);
+  m.def("gnn_lin_ws_grid", &gnn_lin_ws_grid, py::arg("ks"), py::arg("nw"), py::arg("et"), py::arg("bwd"),
+        py::arg("n"));
   m.def("gnn_lin_bwd_image_bytes", &gnn_lin_bwd_image_bytes);
   m.def("gnn_lin_bwd_data", [](uint64_t dy, int lddy, uint64_t ym, int ldym, float mscale, int N, uint64_t w, int K1,
                                int K2, uint64_t dx1, int ldx1, uint64_t dx2, int ldx2, uint64_t rscale, int n,

@@ -405,6 +405,9 @@ __global__ __launch_bounds__(FWD_WAVES * 64) void lin_fwd_kernel(
               const int u = c + e - nsplit;
               if (c + e < N) Yf[(size_t)(u / tk) * n * tk + (size_t)row * tk + u % tk] = v[4 * g + e];
             }
+            // the 16-bit columns [nsplit, ldy) are padding: zero, as without a tail
+            // (c % 4 == 0 and ldy % 8 == 0: the 4 columns lie wholly inside the pitch)
+            if (c < ldy) *reinterpret_cast<uint2*>(Y + (size_t)row * ldy + c) = make_uint2(0u, 0u);
           } else if (c < ldy) {
             *reinterpret_cast<uint2*>(Y + (size_t)row * ldy + c) =
                 pack4e<ET>(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
@@ -1615,7 +1618,43 @@ static int slab_cols(int N, int KP) {
   return cols;
 }
 
+// ---- variant selection: ONE function per launcher decides the kernel family and its
+// template parameters; the launcher dispatches on its answer and the read-only
+// gnn_lin_*_variant queries return it, so a query cannot disagree with a launch.
+enum { LIN_WS = 1, LIN_SLAB = 2, LIN_KC = 3, LIN_GEMM = 4, LIN_WGT2 = 5, LIN_WGT1 = 6 };
+struct LinSel {
+  int fam, a, b;      // fam < 0: the launcher's error code (-1 no variant, -3 bad shape)
+};
+// LIN_WS: a = KS, b = NW.  LIN_SLAB: a = KS (KN), b = 10 * waves per block + staged stores.
+// LIN_KC: a = FG.  LIN_WGT2: a = KT, b = 10 * NB + HAS_YM.  LIN_WGT1: a = KT.
+static int sel_code(LinSel s) { return s.fam < 0 ? s.fam : s.fam * 1000000 + s.a * 1000 + s.b; }
 
+static uint32_t drop_thr8(float p) { return (uint32_t)std::min(255.0, std::floor((double)p * 256.0 + 0.5)); }
+
+// waves per block of the slab kernels
+constexpr int fwd_slab_waves(int KS) { return KS == 16 ? FWD16_WAVES : KS == 8 ? FWD8_WAVES : KS <= 16 ? 16 : 8; }
+constexpr int bwd_slab_waves(int KN) { return KN == 16 ? BWD16_WAVES : KN <= 16 ? 16 : 8; }
+
+// slab geometry: columns per slab, LDS bytes of the image (+ bias for fwd) and whether the
+// per-wave output staging tiles fit beside it
+struct SlabGeom {
+  int cols;
+  size_t lds;
+  bool staged;
+};
+static SlabGeom fwd_slab_geom(int KS, int N, int ldy, bool tail) {
+  const int KP = KS * 16;
+  const int ncols = slab_cols(std::max(N, ldy), KP);
+  const size_t lds = (size_t)ncols * (KP + 8) * 2 + (size_t)ncols * 4;
+  // output staging tiles after the image when they fit beside it (every shape but the widest slabs)
+  return {ncols, lds, !tail && lds + (size_t)fwd_slab_waves(KS) * OST_BYTES <= LDS_MAX};
+}
+static SlabGeom bwd_slab_geom(int KN, int K, bool dx1_f32) {
+  const int NP = KN * 16;
+  const int kcols = slab_cols(K, NP);
+  const size_t lds = (size_t)kcols * (NP + 8) * 2;
+  return {kcols, lds, !dx1_f32 && lds + (size_t)bwd_slab_waves(KN) * OST_BYTES <= LDS_MAX};
+}
 
 template <int KS, int ET>
 static int fwd_launch(const uint16_t* x1, int ld1, int K1, const uint16_t* x2, int ld2, int K2, const float* W, int N,
@@ -1623,9 +1662,10 @@ static int fwd_launch(const uint16_t* x1, int ld1, int K1, const uint16_t* x2, i
                       uint32_t step, uint32_t thr8, uint32_t row0, const int* stepp, const float* rscale,
                       const int* idx1, uint16_t* wimg, float* Yf, int nsplit, int tk, hipStream_t st) {
   constexpr int KP = KS * 16;
-  constexpr int WV = KS == 16 ? FWD16_WAVES : KS == 8 ? FWD8_WAVES : FwdWaves<KS>::value;
-  const int ncols = slab_cols(std::max(N, ldy), KP);
-  const size_t lds = (size_t)ncols * (KP + 8) * 2 + (size_t)ncols * 4;
+  constexpr int WV = fwd_slab_waves(KS);
+  const SlabGeom geo = fwd_slab_geom(KS, N, ldy, Yf != nullptr);
+  const int ncols = geo.cols;
+  const size_t lds = geo.lds;
   {
     const int slabs = (std::max(N, ldy) + ncols - 1) / ncols;
     const long total = (long)slabs * ncols * (KP + 8);
@@ -1633,8 +1673,7 @@ static int fwd_launch(const uint16_t* x1, int ld1, int K1, const uint16_t* x2, i
     hipLaunchKernelGGL(lin_prep_fwd_kernel<ET>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, W, K1 + K2,
                        N, ncols, KP, KP + 8, total, scale, wimg);
   }
-  // output staging tiles after the image when they fit beside it (every shape but the widest slabs)
-  const bool tst = !Yf && lds + (size_t)WV * OST_BYTES <= LDS_MAX;
+  const bool tst = geo.staged;
   const int ost = tst ? (int)lds : -1;
   const size_t lds_all = lds + (tst ? (size_t)WV * OST_BYTES : 0);
   (void)hipFuncSetAttribute((const void*)lin_fwd_kernel<KS, ET, WV>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1667,21 +1706,65 @@ static int kc_launch(const uint16_t* x, int ldx, int K, const float* W, int N, c
   const long total = (long)FG * 128 * KPc;
   hipLaunchKernelGGL(lin_prep_kc_kernel<ET>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, W, K, N, KPc,
                      total, wimg);
-  // the 256 x 256 tiled GEMM where it applies, else the kc kernel
-  if (FG == 2) {
+  // the 256 x 256 tiled GEMM where it applies (two feature groups), else the kc kernel
+  // (`if constexpr`: lin_fwd_kc_kernel<2, *> is never launched, so it is not instantiated)
+  if constexpr (FG == 2) {
     const size_t lds = std::max(sizeof(uint16_t) * 2 * (256 + 256) * 64, (size_t)8 * GEMM_OST_BYTES);
     (void)hipFuncSetAttribute((const void*)lin_gemm_kernel<ET>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL((lin_gemm_kernel<ET>), dim3((n + 255) / 256), dim3(512), lds, st, x, ldx, K, wimg, KPc, bias, Y,
                        ldy, N, n, relu, rscale);
     return (int)hipGetLastError();
+  } else {
+    const int rows_per_block = 4 / FG * 64;
+    hipLaunchKernelGGL((lin_fwd_kc_kernel<FG, ET>), dim3((n + rows_per_block - 1) / rows_per_block), dim3(256), 0, st,
+                       x, ldx, K, wimg, KPc, bias, Y, ldy, N, n, relu, rscale);
+    return (int)hipGetLastError();
   }
-  const int rows_per_block = 4 / FG * 64;
-  hipLaunchKernelGGL((lin_fwd_kc_kernel<FG, ET>), dim3((n + rows_per_block - 1) / rows_per_block), dim3(256), 0, st,
-                     x, ldx, K, wimg, KPc, bias, Y, ldy, N, n, relu, rscale);
-  return (int)hipGetLastError();
 }
 
 // ---- weight-stationary launches (lin_ws_kernel) ----
+template <int KS, int NW, bool BWD>
+constexpr size_t ws_lds() {
+  return 2 * 32 * (KS * 16) * 2 + 2 * 32 * (NW * 64 + 16) + (BWD ? 0 : 2 * 64 * 16 + WS_IDX_TILES * 32 * 4) +
+         WS_IDX_TILES * 32 * 4;
+}
+
+// blocks of the persistent grid for n rows: one per tile up to the chip's resident blocks
+// (occupancy asked once per instantiation)
+template <int KS, int ET, int NW, bool BWD>
+static int ws_grid(int n) {
+  auto kern = lin_ws_kernel<KS, ET, NW, BWD>;
+  constexpr size_t lds = ws_lds<KS, NW, BWD>();
+  static int occ = 0;
+  if (!occ) {
+    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, NW * 64, lds) != hipSuccess || occ < 1) occ = 1;
+  }
+  const int tiles = (n + TILE - 1) / TILE;
+  return std::max(1, std::min(tiles, device_cus() * occ));
+}
+
+// the same for run-time (KS, NW, element type, direction); -1: no such instantiation
+static int ws_grid_rt(int ks, int nw, int et, bool bwd, int n) {
+  if (et != 0 && (et != 1 || bwd)) return -1;
+#define WG(KSV, NWV)                                                                                  \
+  case KSV * 100 + NWV:                                                                               \
+    return bwd ? ws_grid<KSV, 0, NWV, true>(n) : et == 1 ? ws_grid<KSV, 1, NWV, false>(n) : ws_grid<KSV, 0, NWV, false>(n);
+  switch (ks * 100 + nw) {
+    WG(4, 2) WG(4, 4) WG(4, 8) WG(8, 4) WG(8, 8) WG(16, 8)
+    default: return -1;
+  }
+#undef WG
+}
+
+// row ids / row scales of a block's tiles are staged in LDS: at most WS_IDX_TILES tiles per block
+static bool ws_rows_fit(int ks, int nw, int et, bool bwd, int n, bool staged_rows) {
+  if (!staged_rows) return true;
+  const int tiles = (n + TILE - 1) / TILE;
+  const int grid = ws_grid_rt(ks, nw, et, bwd, n);
+  return grid > 0 && (tiles + grid - 1) / grid <= WS_IDX_TILES;
+}
+
 template <int KS, int ET, int NW, bool BWD>
 static int ws_launch(const uint16_t* a1, int lda1, int K1, const uint16_t* a2, int lda2, int K2, const int* idx1,
                      const uint16_t* Ym, int ldym, const float* W, int WK, int WN, const uint16_t* wimg, const float* bias,
@@ -1689,18 +1772,12 @@ static int ws_launch(const uint16_t* a1, int lda1, int K1, const uint16_t* a2, i
                      uint16_t* Y1, int ldy1, int KO1, uint16_t* Y2, int ldy2, int n, int relu, uint32_t k0,
                      uint32_t k1, uint32_t step, uint32_t thr8, uint32_t row0, const int* stepp, const float* rscale,
                      float mscale, hipStream_t st) {
-  constexpr int KP = KS * 16;
-  const size_t lds = 2 * 32 * KP * 2 + 2 * 32 * (NW * 64 + 16) + (BWD ? 0 : 2 * 64 * 16 + WS_IDX_TILES * 32 * 4) +
-                     WS_IDX_TILES * 32 * 4;
+  constexpr size_t lds = ws_lds<KS, NW, BWD>();
   auto kern = lin_ws_kernel<KS, ET, NW, BWD>;
-  static int occ = 0;
-  if (!occ) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, NW * 64, lds) != hipSuccess || occ < 1) occ = 1;
-  }
   const int tiles = (n + TILE - 1) / TILE;
-  const int grid = std::max(1, std::min(tiles, device_cus() * occ));
-  if ((idx1 || rscale) && (tiles + grid - 1) / grid > WS_IDX_TILES) return -4;   // row ids / scales do not fit
+  const int grid = ws_grid<KS, ET, NW, BWD>(n);
+  // row ids / scales do not fit (the selection sends such calls to the slab kernel: never taken)
+  if ((idx1 || rscale) && (tiles + grid - 1) / grid > WS_IDX_TILES) return -4;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a1, lda1, K1, a2, lda2, K2, idx1, Ym, ldym, W, WK, WN, wimg, bias,
                      N, scale, Y1, ldy1, KO1, Y2, ldy2, n, relu, k0, k1, step, thr8, row0, stepp, rscale, mscale);
   return (int)hipGetLastError();
@@ -1719,18 +1796,44 @@ static int ws_waves(int KS, int cols) {
 
 #define WS_DISPATCH(KSV, BWDV, ETV, ...)                                                            \
   {                                                                                                 \
-    int rc_ = -4;                                                                                   \
     switch (KSV * 100 + nw) {                                                                       \
-      case 402: rc_ = ws_launch<4, ETV, 2, BWDV>(__VA_ARGS__); break;                               \
-      case 404: rc_ = ws_launch<4, ETV, 4, BWDV>(__VA_ARGS__); break;                               \
-      case 408: rc_ = ws_launch<4, ETV, 8, BWDV>(__VA_ARGS__); break;                               \
-      case 804: rc_ = ws_launch<8, ETV, 4, BWDV>(__VA_ARGS__); break;                               \
-      case 808: rc_ = ws_launch<8, ETV, 8, BWDV>(__VA_ARGS__); break;                               \
-      case 1608: rc_ = ws_launch<16, ETV, 8, BWDV>(__VA_ARGS__); break;                             \
-      default: break;                                                                               \
+      case 402: return ws_launch<4, ETV, 2, BWDV>(__VA_ARGS__);                                     \
+      case 404: return ws_launch<4, ETV, 4, BWDV>(__VA_ARGS__);                                     \
+      case 408: return ws_launch<4, ETV, 8, BWDV>(__VA_ARGS__);                                     \
+      case 804: return ws_launch<8, ETV, 4, BWDV>(__VA_ARGS__);                                     \
+      case 808: return ws_launch<8, ETV, 8, BWDV>(__VA_ARGS__);                                     \
+      case 1608: return ws_launch<16, ETV, 8, BWDV>(__VA_ARGS__);                                   \
+      default: return -1;                                                                           \
     }                                                                                               \
-    if (rc_ != -4) return rc_;   /* -4: not this form (the slab kernel follows) */                   \
   }
+
+// The forward's variant for one call (n > 0).  Order: the argument checks; the K-chunked
+// forms for a weight too wide for LDS; the weight-stationary form; the slab kernel.
+static LinSel fwd_select(int ld1, int K1, bool x2, int ld2, int K2, int N, int ldy, int n, float p, bool idx1,
+                         bool rscale, bool tail, int nsplit, int tk, int et) {
+  if ((x2 && K1 % 8) || ld1 % 8 || (x2 && (ld2 % 8)) || ldy % 8 || K1 > ld1 || (x2 && K2 > ld2)) return {-3, 0, 0};
+  if (tail ? (nsplit % 4 || nsplit > ldy || nsplit > N || tk <= 0 || (N - nsplit) % tk) : N > ldy) return {-3, 0, 0};
+  if (!x2) K2 = 0;
+  const uint32_t thr8 = drop_thr8(p);
+  const int ks = pick_ks(K1 + K2);
+  if (!x2 && !idx1 && !thr8 && !tail && kc_wanted(K1, N, ldy))
+    return std::max(N, ldy) > 128 ? LinSel{LIN_GEMM, 0, 0} : LinSel{LIN_KC, 1, 0};
+  if (et == 1 && (thr8 || tail)) return {-3, 0, 0};   // fp16: the inference path
+  const int nw = ks > 0 && !tail && !(K1 & 7) && !(K2 & 7) ? ws_waves(ks, std::max(N, ldy)) : 0;
+  if (nw && ws_rows_fit(ks, nw, et, false, n, idx1 || rscale)) return {LIN_WS, ks, nw};
+  if (ks < 0 || ks > (et == 1 ? 48 : 32)) return {-1, 0, 0};
+  return {LIN_SLAB, ks, 10 * fwd_slab_waves(ks) + (fwd_slab_geom(ks, N, ldy, tail).staged ? 1 : 0)};
+}
+
+extern "C" int gnn_lin_fwd_variant(int ld1, int K1, int has_x2, int ld2, int K2, int N, int ldy, int n, float p,
+                                   int has_idx1, int has_rscale, int has_tail, int nsplit, int tk, int et) {
+  return sel_code(fwd_select(ld1, K1, has_x2 != 0, ld2, K2, N, ldy, std::max(n, 1), p, has_idx1 != 0, has_rscale != 0,
+                             has_tail != 0, nsplit, tk, et));
+}
+
+extern "C" int gnn_lin_ws_grid(int ks, int nw, int et, int bwd, int n) {
+  return ws_grid_rt(ks, nw, et, bwd != 0, std::max(n, 1));
+}
 
 // et: element type of X / Y (0 bf16, 1 fp16: the inference path; fp16 takes K <= 768,
 // no dropout or fp32 tail)
@@ -1739,40 +1842,34 @@ extern "C" int gnn_launch_lin_fwd(const void* x1, int ld1, int K1, const void* x
                                   uint32_t k1, uint32_t step, uint32_t row0, const int* stepp, const float* rscale,
                                   const int* idx1, void* wimg, float* Yf, int nsplit, int tk, hipStream_t st, int et) {
   if (n <= 0) return 0;
-  if ((x2 && K1 % 8) || ld1 % 8 || (x2 && (ld2 % 8)) || ldy % 8 || K1 > ld1 || (x2 && K2 > ld2))
-    return -3;
-  if (Yf ? (nsplit % 4 || nsplit > ldy || nsplit > N || tk <= 0 || (N - nsplit) % tk) : N > ldy) return -3;
+  const LinSel sel = fwd_select(ld1, K1, x2 != nullptr, ld2, K2, N, ldy, n, p, idx1 != nullptr, rscale != nullptr,
+                                Yf != nullptr, nsplit, tk, et);
+  if (sel.fam < 0) return sel.fam;
   if (!x2) K2 = 0;
-  const uint32_t thr8 = (uint32_t)std::min(255.0, std::floor((double)p * 256.0 + 0.5));
-  const int ks = pick_ks(K1 + K2);
+  const uint32_t thr8 = drop_thr8(p);
   auto a = (const uint16_t*)x1;
   auto b = (const uint16_t*)x2;
   auto y = (uint16_t*)Y;
-  if (!x2 && !idx1 && !thr8 && !Yf && kc_wanted(K1, N, ldy)) {
-    const int fg = std::max(N, ldy) > 128 ? 2 : 1;
+  if (sel.fam == LIN_KC || sel.fam == LIN_GEMM) {
     auto w = (uint16_t*)wimg;
     if (et == 1)
-      return fg == 2 ? kc_launch<2, 1>(a, ld1, K1, W, N, bias, y, ldy, n, relu, rscale, w, st)
-                     : kc_launch<1, 1>(a, ld1, K1, W, N, bias, y, ldy, n, relu, rscale, w, st);
-    return fg == 2 ? kc_launch<2, 0>(a, ld1, K1, W, N, bias, y, ldy, n, relu, rscale, w, st)
-                   : kc_launch<1, 0>(a, ld1, K1, W, N, bias, y, ldy, n, relu, rscale, w, st);
+      return sel.fam == LIN_GEMM ? kc_launch<2, 1>(a, ld1, K1, W, N, bias, y, ldy, n, relu, rscale, w, st)
+                                 : kc_launch<1, 1>(a, ld1, K1, W, N, bias, y, ldy, n, relu, rscale, w, st);
+    return sel.fam == LIN_GEMM ? kc_launch<2, 0>(a, ld1, K1, W, N, bias, y, ldy, n, relu, rscale, w, st)
+                               : kc_launch<1, 0>(a, ld1, K1, W, N, bias, y, ldy, n, relu, rscale, w, st);
   }
-  {
-    const int nw = !Yf && !(K1 & 7) && !(K2 & 7) ? ws_waves(ks, std::max(N, ldy)) : 0;
-    if (nw) {
-      const float scale = thr8 > 0 ? 1.f / (1.f - p) : 1.f;
-      if (et == 1) {
-        if (thr8) return -3;
-        WS_DISPATCH(ks, false, 1, a, ld1, K1, b, ld2, K2, idx1, nullptr, 0, W, K1 + K2, N, nullptr, bias, N, scale, y, ldy, 0,
-                    nullptr, 0, n, relu, k0, k1, step, thr8, row0, stepp, rscale, 1.f, st)
-      } else {
-        WS_DISPATCH(ks, false, 0, a, ld1, K1, b, ld2, K2, idx1, nullptr, 0, W, K1 + K2, N, nullptr, bias, N, scale, y, ldy, 0,
-                    nullptr, 0, n, relu, k0, k1, step, thr8, row0, stepp, rscale, 1.f, st)
-      }
-    }
+  const int ks = sel.a;
+  if (sel.fam == LIN_WS) {
+    const int nw = sel.b;
+    const float scale = thr8 > 0 ? 1.f / (1.f - p) : 1.f;
+    if (et == 1)
+      WS_DISPATCH(ks, false, 1, a, ld1, K1, b, ld2, K2, idx1, nullptr, 0, W, K1 + K2, N, nullptr, bias, N, scale, y, ldy, 0,
+                  nullptr, 0, n, relu, k0, k1, step, thr8, row0, stepp, rscale, 1.f, st)
+    else
+      WS_DISPATCH(ks, false, 0, a, ld1, K1, b, ld2, K2, idx1, nullptr, 0, W, K1 + K2, N, nullptr, bias, N, scale, y, ldy, 0,
+                  nullptr, 0, n, relu, k0, k1, step, thr8, row0, stepp, rscale, 1.f, st)
   }
   if (et == 1) {
-    if (thr8 || Yf) return -3;
 #define LH(c) if (ks == c) return fwd_launch<c, 1>(a, ld1, K1, b, ld2, K2, W, N, bias, y, ldy, n, relu, p, k0, k1, step, thr8, row0, stepp, rscale, idx1, (uint16_t*)wimg, Yf, nsplit, tk, st);
     LH(4) LH(8) LH(16) LH(24) LH(32) LH(40) LH(48)
 #undef LH
@@ -1790,15 +1887,16 @@ static int bwd_data_launch(const uint16_t* dY, int lddy, const uint16_t* Ym, int
                            const float* rscale, int n, int dx1_f32, uint16_t* wimg, hipStream_t st) {
   constexpr int NP = KN * 16;
   const int K = K1 + K2;
-  const int kcols = slab_cols(K, NP);
-  const size_t lds = (size_t)kcols * (NP + 8) * 2;
+  const SlabGeom geo = bwd_slab_geom(KN, K, dx1_f32 != 0);
+  const int kcols = geo.cols;
+  const size_t lds = geo.lds;
   {
     const long total = (long)((K + kcols - 1) / kcols) * kcols * (NP + 8);
     hipLaunchKernelGGL(lin_prep_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, W, K, N, NP,
                        NP + 8, total, wimg);
   }
-  constexpr int WV = KN == 16 ? BWD16_WAVES : FwdWaves<KN>::value;
-  const bool tst = !dx1_f32 && lds + (size_t)WV * OST_BYTES <= LDS_MAX;
+  constexpr int WV = bwd_slab_waves(KN);
+  const bool tst = geo.staged;
   const int ost = tst ? (int)lds : -1;
   const size_t lds_all = lds + (tst ? (size_t)WV * OST_BYTES : 0);
   (void)hipFuncSetAttribute((const void*)lin_bwd_data_kernel<KN, WV>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1810,19 +1908,40 @@ static int bwd_data_launch(const uint16_t* dY, int lddy, const uint16_t* Ym, int
   return (int)hipGetLastError();
 }
 
+// The data backward's variant for one call (n > 0): the weight-stationary form (bf16 dX1,
+// no chunk straddling N, K1 + K2 <= 256 output columns), else the slab kernel.
+static LinSel bwd_data_select(int lddy, bool Ym, int ldym, int N, int K1, bool dX2, int K2, int ldx1, int ldx2, int n,
+                              bool rscale, bool dx1_f32) {
+  if (lddy % 8 || (Ym && ldym % 8) || (dX2 && K1 % 8) || ldx1 % 8 || (dX2 && ldx2 % 8) || N > lddy) return {-3, 0, 0};
+  if (!dX2) K2 = 0;
+  const int kn = pick_ks(N);
+  const int nw = kn > 0 && !dx1_f32 && !(N & 7) ? ws_waves(kn, K1 + K2) : 0;
+  if (nw && ws_rows_fit(kn, nw, 0, true, n, rscale)) return {LIN_WS, kn, nw};
+  if (kn < 0 || kn > 32) return {-1, 0, 0};
+  return {LIN_SLAB, kn, 10 * bwd_slab_waves(kn) + (bwd_slab_geom(kn, K1 + K2, dx1_f32).staged ? 1 : 0)};
+}
+
+extern "C" int gnn_lin_bwd_data_variant(int lddy, int has_ym, int ldym, int N, int K1, int has_dx2, int K2, int ldx1,
+                                        int ldx2, int n, int has_rscale, int dx1_f32) {
+  return sel_code(bwd_data_select(lddy, has_ym != 0, ldym, N, K1, has_dx2 != 0, K2, ldx1, ldx2, std::max(n, 1),
+                                  has_rscale != 0, dx1_f32 != 0));
+}
+
 extern "C" int gnn_launch_lin_bwd_data(const void* dY, int lddy, const void* Ym, int ldym, float mscale, int N,
                                        const float* W, int K1, int K2, void* dX1, int ldx1, void* dX2, int ldx2,
                                        const float* rscale, int n, int dx1_f32, void* wimg, hipStream_t st) {
   if (n <= 0) return 0;
-  if (lddy % 8 || (Ym && ldym % 8) || (dX2 && K1 % 8) || ldx1 % 8 || (dX2 && ldx2 % 8) || N > lddy) return -3;
+  const LinSel sel = bwd_data_select(lddy, Ym != nullptr, ldym, N, K1, dX2 != nullptr, K2, ldx1, ldx2, n,
+                                     rscale != nullptr, dx1_f32 != 0);
+  if (sel.fam < 0) return sel.fam;
   if (!dX2) K2 = 0;
-  const int kn = pick_ks(N);
+  const int kn = sel.a;
   auto d = (const uint16_t*)dY;
   auto m = (const uint16_t*)Ym;
   auto o1 = (uint16_t*)dX1;
   auto o2 = (uint16_t*)dX2;
   {
-    const int nw = !dx1_f32 && !(N & 7) ? ws_waves(kn, K1 + K2) : 0;
+    const int nw = sel.fam == LIN_WS ? sel.b : 0;
     if (nw) {
       const int NP = kn * 16, rows = nw * 32;
       const long total = (long)rows * (NP + 8);
@@ -1840,21 +1959,31 @@ extern "C" int gnn_launch_lin_bwd_data(const void* dY, int lddy, const void* Ym,
 }
 
 // bytes of the weight images the launchers write (the caller provides the scratch)
-// (upper bounds over every slab width the launchers may pick for any row count:
-// slabs * width < columns + 256)
+// The slab kernels' image holds slabs * width rows with the width slab_cols picks, which
+// reaches 992 columns on a short reduction: two slabs of 992 for 1000 columns.  (The bound
+// used before, columns + 256 rows, held only for widths up to 256: the image kernel wrote,
+// and the second slab's blocks read, past the scratch for e.g. K = 128 x N = 520 forward or
+// N = 8 x K = 1000 backward.)  Never less than that former bound, which also covers the 256
+// rows of the weight-stationary and K-chunked images.
+static long slab_image_rows(int cols, int KP) {
+  const int width = slab_cols(cols, KP);
+  const long slabs = (cols + width - 1) / width;
+  return std::max(slabs * width, (long)(cols + 31) / 32 * 32 + 256);
+}
+
 extern "C" long gnn_lin_fwd_image_bytes(int K, int N, int ldy) {
   const long kc = kc_wanted(K, N, ldy) ? 2L * 256 * kc_pad(K) : 0;
   const int ks = pick_ks(K);
   if (ks < 0) return kc > 0 ? kc : -1;
   const int KP = ks * 16;
-  return std::max(kc, 2L * ((std::max(N, ldy) + 31) / 32 * 32 + 256) * (KP + 8));
+  return std::max(kc, 2L * slab_image_rows(std::max(N, ldy), KP) * (KP + 8));
 }
 
 extern "C" long gnn_lin_bwd_image_bytes(int K, int N) {
   const int kn = pick_ks(N);
   if (kn < 0) return -1;
   const int NP = kn * 16;
-  return 2L * ((K + 31) / 32 * 32 + 256) * (NP + 8);
+  return 2L * slab_image_rows(K, NP) * (NP + 8);
 }
 
 // chunk count of the split-K weight gradient for n rows and N columns (fills the chip)
@@ -1893,15 +2022,51 @@ static int wgt_launch(const uint16_t* x1, int ld1, int K1, const uint16_t* x2, i
 }
 
 constexpr int WGT2_LDS_MAX = 160 * 1024;
+constexpr long wgt2_lds(int kt, int nb) { return 2L * TILE * (wgt2_pitch(kt) + wgt2_pitch(nb)); }   // Wgt2<KT, NB>::LDS
 
-// -1: the staged row ids of a gathered X1 would not fit next to the images (the caller
-// falls back to v1 with the same chunking)
+// the compiled (KT, NB) forms of lin_bwd_weight2, in the order they are tried, and the KT
+// of the v1 kernel
+#define WGT2_VARIANTS(X)                                                                              \
+  X(2, 2) X(2, 4) X(2, 8) X(4, 2) X(4, 4) X(4, 8) X(5, 2) X(5, 4) X(8, 2) X(8, 4) X(8, 8) X(9, 2) X(9, 4)   \
+  X(12, 2) X(12, 4) X(16, 2) X(16, 4) X(17, 2)
+#define WGT1_VARIANTS(X) X(2) X(4) X(5) X(8) X(9) X(12) X(16) X(17)
+
+// The weight gradient's variant for one call: the first lin_bwd_weight2 form that covers
+// the k-tiles with the column tiles wgt2_nb asks for and whose images (plus the staged row
+// ids of a gathered X1) fit LDS; else the v1 kernel with the same chunking.
+static LinSel wgt_select(int ld1, int K1, bool x2, int ld2, int K2, int lddy, bool Ym, int ldym, int N, int n,
+                         bool idx1) {
+  if ((x2 && K1 % 8) || ld1 % 8 || (x2 && ld2 % 8) || lddy % 8 || (Ym && ldym % 8) || N > lddy) return {-3, 0, 0};
+  if (!x2) K2 = 0;
+  const int K = K1 + K2, kt = (K + 31) / 32;
+  const int chunks = gnn_lin_wgrad_chunks(std::max(n, 1), N, K);
+  const int tiles = (std::max(n, 1) + TILE - 1) / TILE;
+  const long rpc = (tiles + chunks - 1) / chunks * TILE;
+  const int nb = wgt2_nb(kt, N);
+#define X(c, b_) if (kt <= c && nb == b_ && wgt2_lds(c, b_) + (idx1 ? 4L * rpc : 0L) <= WGT2_LDS_MAX) return {LIN_WGT2, c, 10 * b_ + (Ym ? 1 : 0)};
+  WGT2_VARIANTS(X)
+#undef X
+#define X(c) if (kt <= c) return {LIN_WGT1, c, 0};
+  WGT1_VARIANTS(X)
+#undef X
+  return {-1, 0, 0};
+}
+
+extern "C" int gnn_lin_bwd_weight_variant(int ld1, int K1, int has_x2, int ld2, int K2, int lddy, int has_ym, int ldym,
+                                          int N, int n, int has_idx1) {
+  return sel_code(wgt_select(ld1, K1, has_x2 != 0, ld2, K2, lddy, has_ym != 0, ldym, N, n, has_idx1 != 0));
+}
+
+// -1: the staged row ids of a gathered X1 would not fit next to the images.  wgt_select
+// sends such calls to the next form or to v1, so this is never taken; kept as a guard of the
+// LDS size, and an error to the caller (no fall-back from here) if it ever fires
 template <int KT, int NB, bool HAS_YM>
 static int wgt2_launch_t(const uint16_t* x1, int ld1, int K1, const uint16_t* x2, int ld2, int K2, const uint16_t* dY,
                          int lddy, const uint16_t* Ym, int ldym, float mscale, int N, float* gpart, int n, int chunks,
                          const int* idx1, hipStream_t st) {
   const int tiles = (n + TILE - 1) / TILE;
   const int rpc = (tiles + chunks - 1) / chunks * TILE;
+  static_assert(Wgt2<KT, NB>::LDS == wgt2_lds(KT, NB), "wgt_select sizes the images with wgt2_lds");
   const long lds = Wgt2<KT, NB>::LDS + (idx1 ? 4L * rpc : 0L);
   if (lds > WGT2_LDS_MAX) return -1;
   static const bool attr = [] {
@@ -1930,31 +2095,24 @@ static int wgt2_launch(const uint16_t* x1, int ld1, int K1, const uint16_t* x2, 
 extern "C" int gnn_launch_lin_bwd_weight(const void* x1, int ld1, int K1, const void* x2, int ld2, int K2,
                                          const void* dY, int lddy, const void* Ym, int ldym, float mscale, int N,
                                          float* gpart, float* dW, float* db, int n, const int* idx1, hipStream_t st) {
-  if ((x2 && K1 % 8) || ld1 % 8 || (x2 && ld2 % 8) || lddy % 8 || (Ym && ldym % 8) || N > lddy) return -3;
+  const LinSel sel = wgt_select(ld1, K1, x2 != nullptr, ld2, K2, lddy, Ym != nullptr, ldym, N, n, idx1 != nullptr);
+  if (sel.fam == -3) return -3;
   if (!x2) K2 = 0;
   const int K = K1 + K2;
   const int chunks = gnn_lin_wgrad_chunks(std::max(n, 1), N, K);
   if (n > 0) {
-    const int kt = (K + 31) / 32;
+    if (sel.fam < 0) return sel.fam;
     auto a = (const uint16_t*)x1;
     auto b = (const uint16_t*)x2;
     auto d = (const uint16_t*)dY;
     auto m = (const uint16_t*)Ym;
     int rc = -1;
-    {
-      const int nb = wgt2_nb(kt, N);
-#define LW2(c, b_) if (rc == -1 && kt <= c && nb == b_) rc = wgt2_launch<c, b_>(a, ld1, K1, b, ld2, K2, d, lddy, m, ldym, mscale, N, gpart, n, chunks, idx1, st);
-      LW2(2, 2) LW2(2, 4) LW2(2, 8) LW2(4, 2) LW2(4, 4) LW2(4, 8) LW2(5, 2) LW2(5, 4)
-      LW2(8, 2) LW2(8, 4) LW2(8, 8) LW2(9, 2) LW2(9, 4) LW2(12, 2) LW2(12, 4) LW2(16, 2) LW2(16, 4) LW2(17, 2)
-#undef LW2
-      if (rc == -1) rc = -2;                 // no v2 form: v1 below
-    }
-    if (rc == -2) {
-      rc = -1;
-#define LW(c) if (rc == -1 && kt <= c) rc = wgt_launch<c>(a, ld1, K1, b, ld2, K2, d, lddy, m, ldym, mscale, N, gpart, n, chunks, idx1, st);
-      LW(2) LW(4) LW(5) LW(8) LW(9) LW(12) LW(16) LW(17)
-#undef LW
-    }
+#define X(c, b_) if (sel.fam == LIN_WGT2 && sel.a == c && sel.b / 10 == b_) rc = wgt2_launch<c, b_>(a, ld1, K1, b, ld2, K2, d, lddy, m, ldym, mscale, N, gpart, n, chunks, idx1, st);
+    WGT2_VARIANTS(X)
+#undef X
+#define X(c) if (sel.fam == LIN_WGT1 && sel.a == c) rc = wgt_launch<c>(a, ld1, K1, b, ld2, K2, d, lddy, m, ldym, mscale, N, gpart, n, chunks, idx1, st);
+    WGT1_VARIANTS(X)
+#undef X
     if (rc != 0) return rc;
   } else {
     (void)hipMemsetAsync(gpart, 0, sizeof(float) * (size_t)(K + 1) * N * chunks, st);

@@ -70,7 +70,8 @@ def lin_fwd(x1: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = No
     (default ``len(idx1)`` or the rows of x2 / x1).
     ``tail`` (fp32, with ``nsplit``): the columns ``c >= nsplit`` are written exactly, as
     planes of ``tk`` columns -- ``tail[(c - nsplit) // tk, row, (c - nsplit) % tk]`` --
-    instead of bf16 into ``out`` (whose columns then stop at ``nsplit``)."""
+    instead of bf16 into ``out`` (whose columns then stop at ``nsplit``; the columns
+    ``nsplit..ldy`` are written as zeros, like the padding without a tail)."""
     if n is None:
         n = idx1.shape[0] if idx1 is not None else (x2.shape[0] if x2 is not None else x1.shape[0])
     K1 = x1.shape[1] if K1 is None else int(K1)
