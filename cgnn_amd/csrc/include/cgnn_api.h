@@ -225,6 +225,11 @@ int gnn_launch_gat_row_ce(const float* Z, int ldz, const float* bias, int C, con
                           float* db, long n, hipStream_t st);
 int gnn_launch_gat_pack_grad(const float* dWh, const float* ds_src, const float* ds_dst, int HF, int K, void* dy,
                              int ldy, long n, hipStream_t st);
+// Read-only query (host only): the aggregation kernels' variant for K heads of width Fh, by
+// the selection function the three launchers dispatch on: L * 100 + G (L lanes per row, G
+// lanes per head); -3 a shape outside the rule (Fh % 8 == 0, Fh / 8 a power of two with
+// several heads, K * Fh <= 512), -1 a pair that is not compiled.
+int gnn_gat_variant(int K, int Fh);
 int gnn_launch_gat_fwd(const int* rowptr, const int* col, const void* Wh, const float* s_src, const float* s_dst,
                        const int* dst_rows, float* out, float* lse, void* q, int n, int K, int Fh, int wbf,
                        const float* bias, void* H, int ldh, float p, uint32_t k0, uint32_t k1, uint32_t step,

@@ -351,6 +351,7 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("n"), py::arg("K"), py::arg("Fh"), py::arg("st"), py::arg("wbf") = 0, py::arg("dst_rows") = 0,
      py::arg("q") = 0, py::arg("bias") = 0, py::arg("H") = 0, py::arg("ldh") = 0, py::arg("p") = 0.f,
      py::arg("k0") = 0, py::arg("k1") = 0, py::arg("step") = 0, py::arg("stepp") = 0, py::arg("row0") = 0);
+  m.def("gnn_gat_variant", &gnn_gat_variant, py::arg("K"), py::arg("Fh"));
   m.def("gnn_gat_row_blocks", &gnn_gat_row_blocks);
   m.def("gnn_gat_rows", [](int act, uint64_t dout, int ldh, uint64_t out, uint64_t q, uint64_t lse, uint64_t sd,
                            uint64_t dst_rows, uint64_t rstat, uint64_t dsd, uint64_t dy, int ldy, uint64_t dout_w,

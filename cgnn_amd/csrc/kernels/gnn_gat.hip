@@ -582,6 +582,11 @@ __global__ __launch_bounds__(256) void gat_row_ce_kernel(const float* __restrict
           if (dZb) dZb[(size_t)row * ldz + c] = (uint16_t)bf16u(d);
         }
       }
+      // pad columns past the lanes' slots (a stride wider than 64 * CP)
+      for (int c = lane + 64 * CP; c < ldz; c += 64) {
+        if (dZ) dZ[(size_t)row * ldz + c] = 0.f;
+        if (dZb) dZb[(size_t)row * ldz + c] = 0;
+      }
     }
   }
   if (lane == 0) {
@@ -700,34 +705,42 @@ int lanes_for(int HF) {
 constexpr int GAT_EC = 2;
 #define GAT_EC_OF(L) ((L) < GAT_EC ? (L) : GAT_EC)
 
+// The compiled (L, G) pairs: every pair the shape rule can produce (Fh % 8 == 0, Fh / 8 a
+// power of two with several heads, K * Fh <= 512).  Several heads: K * G <= L, so G <= L / 2;
+// one head: G = L.  One list for the query and for the three launchers' switches.
+#define GAT_PAIRS(X, A)                                                                     \
+  X(A, 8, 1) X(A, 8, 2) X(A, 8, 4) X(A, 8, 8)                                              \
+  X(A, 16, 1) X(A, 16, 2) X(A, 16, 4) X(A, 16, 8) X(A, 16, 16)                             \
+  X(A, 32, 1) X(A, 32, 2) X(A, 32, 4) X(A, 32, 8) X(A, 32, 16) X(A, 32, 32)                \
+  X(A, 64, 1) X(A, 64, 2) X(A, 64, 4) X(A, 64, 8) X(A, 64, 16) X(A, 64, 32) X(A, 64, 64)
+#define GAT_KNOWN(A, l, g) case l * 100 + g:
+#define GAT_CASE(LAUNCH, l, g) case l * 100 + g: LAUNCH(l, g); break;
 #define GAT_SWITCH(LAUNCH)                                                                  \
-  switch (L * 100 + G) {                                                                   \
-    case 801: LAUNCH(8, 1); break;                                                         \
-    case 802: LAUNCH(8, 2); break;                                                         \
-    case 804: LAUNCH(8, 4); break;                                                         \
-    case 808: LAUNCH(8, 8); break;                                                         \
-    case 1601: LAUNCH(16, 1); break;                                                       \
-    case 1602: LAUNCH(16, 2); break;                                                       \
-    case 1604: LAUNCH(16, 4); break;                                                       \
-    case 1608: LAUNCH(16, 8); break;                                                       \
-    case 1616: LAUNCH(16, 16); break;                                                      \
-    case 3202: LAUNCH(32, 2); break;                                                       \
-    case 3204: LAUNCH(32, 4); break;                                                       \
-    case 3208: LAUNCH(32, 8); break;                                                       \
-    case 3216: LAUNCH(32, 16); break;                                                      \
-    case 3232: LAUNCH(32, 32); break;                                                      \
-    case 6404: LAUNCH(64, 4); break;                                                       \
-    case 6408: LAUNCH(64, 8); break;                                                       \
-    case 6416: LAUNCH(64, 16); break;                                                      \
-    case 6464: LAUNCH(64, 64); break;                                                      \
+  switch (variant) {                                                                       \
+    GAT_PAIRS(GAT_CASE, LAUNCH)                                                            \
     default: return -1;                                                                    \
   }
 
-// geometry shared by the launchers: one head -> its group is the row's whole sub-group
+// The kernel variant of a (heads, head width): L * 100 + G with L lanes per row (L * 8 >=
+// K * Fh) and G lanes per head (one head: its group is the row's whole sub-group); -3 a
+// shape outside the rule, -1 a pair that is not compiled.  Host only; the launchers
+// dispatch on this value.
+extern "C" int gnn_gat_variant(int K, int Fh) {
+  if (K < 1 || Fh < 8 || Fh % 8 || (long)K * Fh > 512) return -3;
+  const int L = lanes_for(K * Fh), G = K == 1 ? L : Fh / 8;
+  if (L < 0 || (K > 1 && (G & (G - 1)))) return -3;
+  switch (L * 100 + G) {
+    GAT_PAIRS(GAT_KNOWN, )
+      return L * 100 + G;
+    default: return -1;
+  }
+}
+
+// geometry shared by the launchers
 #define GAT_GEOM                                                                            \
-  const int HF = K * Fh;                                                                   \
-  const int L = lanes_for(HF), G = K == 1 ? L : Fh / 8;                                    \
-  if (L < 0 || Fh % 8 || (K > 1 && (G & (G - 1)))) return -3;                              \
+  const int variant = gnn_gat_variant(K, Fh);                                              \
+  if (variant < 0) return variant;                                                         \
+  const int HF = K * Fh, L = variant / 100;                                                \
   const int rpb = 4 * (64 / L);
 
 namespace {
