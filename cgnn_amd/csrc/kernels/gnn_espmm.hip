@@ -14,7 +14,7 @@
 //                   dval[e]  = <g, m_e>      (m_e as in the forward, after the ReLU)
 //                 the gradient with respect to the edge rows and the edge values.
 //
-// Mapping (gnn_wspmm.hip's): wave64, a sub-group of L lanes owns one row, each lane owns 8
+// Mapping (gnn_launch.h's): wave64, a sub-group of L lanes owns one row, each lane owns 8
 // consecutive features (one 16-byte load per bf16 / fp16 row), L = 8 / 16 / 32 / 64 for
 // widths up to 64 / 128 / 256 / 512; wider rows run as 512-column slabs in the launchers.
 // The ids and values of a chunk of L edges come with one coalesced load per lane,
@@ -33,10 +33,11 @@
 #include "cgnn_common.h"
 #include "cgnn_api.h"
 #include "gnn_gather.h"
-#include <algorithm>
+#include "gnn_launch.h"
 
 using namespace cgnn;
 using namespace cgnn::gather;
+using namespace cgnn::launch;
 
 namespace {
 
@@ -295,38 +296,15 @@ __global__ __launch_bounds__(256) void egrad_kernel(
 }
 
 // ---------------------------------------------------------------- launchers
-template <int L, int MODE>
-static int espmm_dispatch(const int* rowptr, const int* col, const float* val, const int* eperm, const void* X,
-                          const void* E, void* Y, int n_rows, int F, int ldx, int lde, int ldy, int t, int relu,
-                          int wc, hipStream_t st) {
-  constexpr int RPB = 4 * (64 / L);               // rows per 256-thread block
-  dim3 grid((n_rows + RPB - 1) / RPB), block(256);
-#define CGNN_ESPMM(T)                                                                                        \
-  hipLaunchKernelGGL((espmm_kernel<L, T, MODE>), grid, block, 0, st, rowptr, col, val, eperm, X, E, Y, n_rows, \
-                     F, ldx, lde, ldy, relu, wc)
-  // element-type codes: 0 fp32, 1 bf16, 2 fp16
-  if (t == 0) CGNN_ESPMM(0);
-  else if (t == 1) CGNN_ESPMM(1);
-  else if (t == 2) CGNN_ESPMM(2);
-  else return -5;
-#undef CGNN_ESPMM
-  return (int)hipGetLastError();
-}
+// (lane dispatch, grid, type table and the slab walk: gnn_launch.h)
 
-// one launch writing output columns [0, wc) of its base (wc <= 512)
-template <int MODE>
-static int espmm_launch(const int* rowptr, const int* col, const float* val, const int* eperm, const void* X,
-                        const void* E, void* Y, int n_rows, int F, int ldx, int lde, int ldy, int t, int relu,
-                        int wc, hipStream_t st) {
-  const int w = std::max(F, wc);
-  if (w <= 64) return espmm_dispatch<8, MODE>(rowptr, col, val, eperm, X, E, Y, n_rows, F, ldx, lde, ldy, t, relu, wc, st);
-  if (w <= 128) return espmm_dispatch<16, MODE>(rowptr, col, val, eperm, X, E, Y, n_rows, F, ldx, lde, ldy, t, relu, wc, st);
-  if (w <= 256) return espmm_dispatch<32, MODE>(rowptr, col, val, eperm, X, E, Y, n_rows, F, ldx, lde, ldy, t, relu, wc, st);
-  if (w <= 512) return espmm_dispatch<64, MODE>(rowptr, col, val, eperm, X, E, Y, n_rows, F, ldx, lde, ldy, t, relu, wc, st);
-  return -1;
+// fn(Const<MODE>) for the MODE of both kernels: the sum of edge rows without X, else the op
+template <class Fn>
+static int with_mode(const void* X, int op, Fn&& fn) {
+  if (X && op != 1) return fn(Const<kAdd>{});
+  if (X) return fn(Const<kMul>{});
+  return fn(Const<kEdgeOnly>{});
 }
-
-static bool stride_ok(int ld, int F) { return ld > 0 && ld % 8 == 0 && F <= ld; }
 
 // op: 0 add, 1 mul; X may be null (the sum of edge rows; op and ldx are then ignored).
 // No allocation and no synchronisation: capturable into a hipGraph.  Return codes: see
@@ -334,59 +312,28 @@ static bool stride_ok(int ld, int F) { return ld > 0 && ld % 8 == 0 && F <= ld; 
 extern "C" int gnn_launch_espmm(const int* rowptr, const int* col, const float* val, const int* eperm,
                                 const void* X, const void* E, void* Y, int n_rows, int F, int ldx, int lde, int ldy,
                                 int t, int op, int relu, hipStream_t st) {
-  constexpr int slab = 512;
   if (F < 0 || !E || !Y || !stride_ok(lde, F) || !stride_ok(ldy, F) || (X && !stride_ok(ldx, F))) return -3;
   if (relu && op == 1) return -3;
-  if (t < 0 || t > 2) return -5;
+  if (!type_ok(t)) return -5;
   if (op != 0 && op != 1) return -1;
   if (n_rows <= 0) return 0;
-  const int mode = !X ? kEdgeOnly : op == 1 ? kMul : kAdd;
-  if (mode == kEdgeOnly) relu = 0;
-  const size_t es = t ? 2 : 4;
-  // wide rows: column slabs of 512 output columns (16-byte aligned offsets), one launch
-  // each; the last slabs also write the padding columns up to ldy
-  for (int c0 = 0; c0 < ldy; c0 += slab) {
-    const int fc = std::max(0, std::min(slab, F - c0));
-    const int wc = std::min(slab, ldy - c0);
-    const void* x = X ? (const char*)X + (fc ? c0 * es : 0) : nullptr;
-    const void* e = (const char*)E + (fc ? c0 * es : 0);
-    void* y = (char*)Y + c0 * es;
-    int rc;
-    if (mode == kAdd) rc = espmm_launch<kAdd>(rowptr, col, val, eperm, x, e, y, n_rows, fc, ldx, lde, ldy, t, relu, wc, st);
-    else if (mode == kMul) rc = espmm_launch<kMul>(rowptr, col, val, eperm, x, e, y, n_rows, fc, ldx, lde, ldy, t, relu, wc, st);
-    else rc = espmm_launch<kEdgeOnly>(rowptr, col, val, eperm, x, e, y, n_rows, fc, ldx, lde, ldy, t, relu, wc, st);
-    if (rc) return rc;
-  }
-  return 0;
-}
-
-template <int L, int MODE>
-static int egrad_dispatch(const int* rowptr, const int* col, const float* val, const void* dY, const void* X,
-                          const void* E, void* dE, float* dval, int n_rows, int F, int lddy, int ldx, int lde,
-                          int ldde, int t, int relu, int wc, int first, hipStream_t st) {
-  constexpr int RPB = 4 * (64 / L);
-  dim3 grid((n_rows + RPB - 1) / RPB), block(256);
-#define CGNN_EGRAD(T)                                                                                        \
-  hipLaunchKernelGGL((egrad_kernel<L, T, MODE>), grid, block, 0, st, rowptr, col, val, dY, X, E, dE, dval,   \
-                     n_rows, F, lddy, ldx, lde, ldde, relu, wc, first)
-  if (t == 0) CGNN_EGRAD(0);
-  else if (t == 1) CGNN_EGRAD(1);
-  else if (t == 2) CGNN_EGRAD(2);
-  else return -5;
-#undef CGNN_EGRAD
-  return (int)hipGetLastError();
-}
-
-template <int MODE>
-static int egrad_launch(const int* rowptr, const int* col, const float* val, const void* dY, const void* X,
-                        const void* E, void* dE, float* dval, int n_rows, int F, int lddy, int ldx, int lde,
-                        int ldde, int t, int relu, int wc, int first, hipStream_t st) {
-  const int w = std::max(F, wc);
-  if (w <= 64) return egrad_dispatch<8, MODE>(rowptr, col, val, dY, X, E, dE, dval, n_rows, F, lddy, ldx, lde, ldde, t, relu, wc, first, st);
-  if (w <= 128) return egrad_dispatch<16, MODE>(rowptr, col, val, dY, X, E, dE, dval, n_rows, F, lddy, ldx, lde, ldde, t, relu, wc, first, st);
-  if (w <= 256) return egrad_dispatch<32, MODE>(rowptr, col, val, dY, X, E, dE, dval, n_rows, F, lddy, ldx, lde, ldde, t, relu, wc, first, st);
-  if (w <= 512) return egrad_dispatch<64, MODE>(rowptr, col, val, dY, X, E, dE, dval, n_rows, F, lddy, ldx, lde, ldde, t, relu, wc, first, st);
-  return -1;
+  if (!X) relu = 0;
+  return for_slabs(F, ldy, [&](int c0, int fc, int wc) {
+    const void* x = in_at(X, t, c0, fc);
+    const void* e = in_at(E, t, c0, fc);
+    void* y = out_at(Y, t, c0);
+    return with_mode(X, op, [&](auto m) {
+      constexpr int MODE = decltype(m)::value;
+      return with_lanes(std::max(fc, wc), [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        return with_type(t, [&](auto tt) {
+          hipLaunchKernelGGL((espmm_kernel<L, decltype(tt)::value, MODE>), dim3(blocks(L, n_rows)), dim3(256), 0, st,
+                             rowptr, col, val, eperm, x, e, y, n_rows, fc, ldx, lde, ldy, relu, wc);
+          return (int)hipGetLastError();
+        });
+      });
+    });
+  });
 }
 
 // dE (storage type t, [nnz, ldde]) and dval (fp32 [nnz]) may each be null, not both; X may
@@ -395,37 +342,36 @@ static int egrad_launch(const int* rowptr, const int* col, const float* val, con
 extern "C" int gnn_launch_egrad(const int* rowptr, const int* col, const float* val, const void* dY, const void* X,
                                 const void* E, void* dE, float* dval, int n_rows, int F, int lddy, int ldx, int lde,
                                 int ldde, int t, int op, int relu, hipStream_t st) {
-  constexpr int slab = 512;
   if (F < 0 || !E || !dY || (!dE && !dval) || !stride_ok(lddy, F) || !stride_ok(lde, F) ||
       (X && !stride_ok(ldx, F)) || (dE && !stride_ok(ldde, F)))
     return -3;
   if (relu && op == 1) return -3;
-  if (t < 0 || t > 2) return -5;
+  if (!type_ok(t)) return -5;
   if (op != 0 && op != 1) return -1;
   if (n_rows <= 0) return 0;
-  const int mode = !X ? kEdgeOnly : op == 1 ? kMul : kAdd;
-  if (mode == kEdgeOnly) relu = 0;
-  const size_t es = t ? 2 : 4;
-  // column slabs of 512: the feature slabs in order (dval is their ordered sum), then any
-  // slab that holds only padding columns of dE
-  const int width = std::max({F, dE ? ldde : 0, 1});
-  for (int c0 = 0; c0 < width; c0 += slab) {
-    const int fc = std::max(0, std::min(slab, F - c0));
-    const int wc = dE ? std::max(0, std::min(slab, ldde - c0)) : 0;
-    const size_t off = fc ? c0 * es : 0;
-    const void* dy = (const char*)dY + off;
-    const void* x = X ? (const char*)X + off : nullptr;
-    const void* e = (const char*)E + off;
-    void* de = dE ? (char*)dE + c0 * es : nullptr;
+  if (!X) relu = 0;
+  // the feature slabs in order (dval is their ordered sum), then any slab that holds only
+  // padding columns of dE; the dE width of a slab is derived here (0 without dE)
+  return for_slabs(F, std::max({F, dE ? ldde : 0, 1}), [&](int c0, int fc, int) {
+    const int wc = dE ? std::max(0, std::min(kSlab, ldde - c0)) : 0;
+    const void* dy = in_at(dY, t, c0, fc);
+    const void* x = in_at(X, t, c0, fc);
+    const void* e = in_at(E, t, c0, fc);
+    void* de = dE ? out_at(dE, t, c0) : nullptr;
     float* dv = (fc || c0 == 0) ? dval : nullptr;
-    if (!de && !dv) continue;
+    if (!de && !dv) return 0;                     // neither dE columns nor dval in this slab
     if (!wc) de = nullptr;
     const int first = c0 == 0;
-    int rc;
-    if (mode == kAdd) rc = egrad_launch<kAdd>(rowptr, col, val, dy, x, e, de, dv, n_rows, fc, lddy, ldx, lde, ldde, t, relu, wc, first, st);
-    else if (mode == kMul) rc = egrad_launch<kMul>(rowptr, col, val, dy, x, e, de, dv, n_rows, fc, lddy, ldx, lde, ldde, t, relu, wc, first, st);
-    else rc = egrad_launch<kEdgeOnly>(rowptr, col, val, dy, x, e, de, dv, n_rows, fc, lddy, ldx, lde, ldde, t, relu, wc, first, st);
-    if (rc) return rc;
-  }
-  return 0;
+    return with_mode(X, op, [&](auto m) {
+      constexpr int MODE = decltype(m)::value;
+      return with_lanes(std::max(fc, wc), [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        return with_type(t, [&](auto tt) {
+          hipLaunchKernelGGL((egrad_kernel<L, decltype(tt)::value, MODE>), dim3(blocks(L, n_rows)), dim3(256), 0, st,
+                             rowptr, col, val, dy, x, e, de, dv, n_rows, fc, lddy, ldx, lde, ldde, relu, wc, first);
+          return (int)hipGetLastError();
+        });
+      });
+    });
+  });
 }

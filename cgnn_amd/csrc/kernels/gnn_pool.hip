@@ -15,7 +15,7 @@
 // has the input's storage type: the value is a copy of an input element (16-bit inputs are
 // compared as fp32, an exact conversion both ways), so the result is exact in every type.
 //
-// Mapping (gnn_wspmm.hip's): wave64, a sub-group of L lanes owns one row, each lane owns 8
+// Mapping (gnn_launch.h's): wave64, a sub-group of L lanes owns one row, each lane owns 8
 // consecutive features (one 16-byte load per gathered bf16 / fp16 row, two for fp32), L =
 // 8 / 16 / 32 / 64 for widths up to 64 / 128 / 256 / 512; wider rows run as 512-column
 // slabs in the launchers.  The ids of a chunk of L edges come with one coalesced load per
@@ -32,10 +32,11 @@
 #include "cgnn_common.h"
 #include "cgnn_api.h"
 #include "gnn_gather.h"
-#include <algorithm>
+#include "gnn_launch.h"
 
 using namespace cgnn;
 using namespace cgnn::gather;
+using namespace cgnn::launch;
 
 namespace {
 
@@ -228,121 +229,61 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(
 }
 
 // ---------------------------------------------------------------- launchers
-template <int L>
-static int pool_fwd_dispatch(const int* rowptr, const int* col, const void* X, void* Y, int* arg, int n_rows, int F,
-                             int ldx, int ldy, int ldarg, int t, int is_min, int wy, int wa, hipStream_t st) {
-  constexpr int RPB = 4 * (64 / L);               // rows per 256-thread block
-  dim3 grid((n_rows + RPB - 1) / RPB), block(256);
-#define CGNN_POOL(T, MIN)                                                                                    \
-  hipLaunchKernelGGL((pool_fwd_kernel<L, T, MIN>), grid, block, 0, st, rowptr, col, X, Y, arg, n_rows, F, ldx, \
-                     ldy, ldarg, wy, wa)
-  // element-type codes: 0 fp32, 1 bf16, 2 fp16
-  if (t == 0 && !is_min) CGNN_POOL(0, false);
-  else if (t == 0) CGNN_POOL(0, true);
-  else if (t == 1 && !is_min) CGNN_POOL(1, false);
-  else if (t == 1) CGNN_POOL(1, true);
-  else if (t == 2 && !is_min) CGNN_POOL(2, false);
-  else if (t == 2) CGNN_POOL(2, true);
-  else return -5;
-#undef CGNN_POOL
-  return (int)hipGetLastError();
-}
-
-// one launch writing columns [0, wy) of Y and [0, wa) of arg from their bases (<= 512 each)
-static int pool_fwd_launch(const int* rowptr, const int* col, const void* X, void* Y, int* arg, int n_rows, int F,
-                           int ldx, int ldy, int ldarg, int t, int is_min, int wy, int wa, hipStream_t st) {
-  const int w = std::max(F, std::max(wy, wa));
-  if (w <= 64) return pool_fwd_dispatch<8>(rowptr, col, X, Y, arg, n_rows, F, ldx, ldy, ldarg, t, is_min, wy, wa, st);
-  if (w <= 128) return pool_fwd_dispatch<16>(rowptr, col, X, Y, arg, n_rows, F, ldx, ldy, ldarg, t, is_min, wy, wa, st);
-  if (w <= 256) return pool_fwd_dispatch<32>(rowptr, col, X, Y, arg, n_rows, F, ldx, ldy, ldarg, t, is_min, wy, wa, st);
-  if (w <= 512) return pool_fwd_dispatch<64>(rowptr, col, X, Y, arg, n_rows, F, ldx, ldy, ldarg, t, is_min, wy, wa, st);
-  return -1;
-}
+// (lane dispatch, grid, type tables and the slab walk: gnn_launch.h)
 
 // X and Y share the storage type t; arg (int32, row stride ldarg) may be null (inference).
 // No allocation and no synchronisation: capturable into a hipGraph.  Return codes: see
 // cgnn_api.h.
 extern "C" int gnn_launch_pool_fwd(const int* rowptr, const int* col, const void* X, void* Y, int* arg, int n_rows,
                                    int F, int ldx, int ldy, int ldarg, int t, int is_min, hipStream_t st) {
-  constexpr int slab = 512;
-  if (ldx <= 0 || ldy <= 0 || (ldx % 8) || (ldy % 8) || F < 0 || F > ldx || F > ldy) return -3;
-  if (arg && (ldarg <= 0 || (ldarg % 8) || F > ldarg)) return -3;
-  if (t < 0 || t > 2) return -5;
+  if (F < 0 || !stride_ok(ldx, F) || !stride_ok(ldy, F)) return -3;
+  if (arg && !stride_ok(ldarg, F)) return -3;
+  if (!type_ok(t)) return -5;
   if (n_rows <= 0) return 0;
   if (!rowptr || !X || !Y) return -3;
+  // two written widths: the walk covers the wider, each slab writes [0, wy) of Y and
+  // [0, wa) of arg from their bases
   const int lda = arg ? ldarg : 0;
-  const int wmax = std::max(ldy, lda);
-  if (wmax <= slab) return pool_fwd_launch(rowptr, col, X, Y, arg, n_rows, F, ldx, ldy, ldarg, t, is_min, ldy, lda, st);
-  // wide rows: column slabs of 512 output columns (16-byte aligned offsets), one launch
-  // each; the last slabs also write the padding columns up to ldy / ldarg
-  const size_t es = t ? 2 : 4;
-  for (int c0 = 0; c0 < wmax; c0 += slab) {
-    const int fc = std::max(0, std::min(slab, F - c0));
-    const int wy = std::max(0, std::min(slab, ldy - c0));
-    const int wa = std::max(0, std::min(slab, lda - c0));
-    const int rc = pool_fwd_launch(rowptr, col, (const char*)X + (fc ? c0 * es : 0), (char*)Y + (wy ? c0 * es : 0),
-                                   arg && wa ? arg + c0 : nullptr, n_rows, fc, ldx, ldy, ldarg, t, is_min, wy, wa, st);
-    if (rc) return rc;
-  }
-  return 0;
-}
-
-template <int L>
-static int pool_bwd_dispatch(const int* rowptr_t, const int* col_t, const int* eperm, const int* arg, const void* dY,
-                             void* dX, int n_src, int F, int ldarg, int lddy, int lddx, int tdy, int tdx, int wc,
-                             hipStream_t st) {
-  constexpr int RPB = 4 * (64 / L);
-  dim3 grid((n_src + RPB - 1) / RPB), block(256);
-#define CGNN_POOL_BWD(TDY, TDX)                                                                                \
-  hipLaunchKernelGGL((pool_bwd_kernel<L, TDY, TDX>), grid, block, 0, st, rowptr_t, col_t, eperm, arg, dY, dX, \
-                     n_src, F, ldarg, lddy, lddx, wc)
-  if (tdy == 1 && tdx == 1) CGNN_POOL_BWD(1, 1);
-  else if (tdy == 1 && tdx == 0) CGNN_POOL_BWD(1, 0);
-  else if (tdy == 2 && tdx == 2) CGNN_POOL_BWD(2, 2);
-  else if (tdy == 2 && tdx == 0) CGNN_POOL_BWD(2, 0);
-  else if (tdy == 0 && tdx == 0) CGNN_POOL_BWD(0, 0);
-  else return -5;
-#undef CGNN_POOL_BWD
-  return (int)hipGetLastError();
-}
-
-// the (dY, dX) type pairs of gnn_launch_wspmm
-static bool pool_pair_ok(int tdy, int tdx) {
-  return (tdy == 1 && (tdx == 1 || tdx == 0)) || (tdy == 2 && (tdx == 2 || tdx == 0)) || (tdy == 0 && tdx == 0);
-}
-
-static int pool_bwd_launch(const int* rowptr_t, const int* col_t, const int* eperm, const int* arg, const void* dY,
-                           void* dX, int n_src, int F, int ldarg, int lddy, int lddx, int tdy, int tdx, int wc,
-                           hipStream_t st) {
-  const int w = std::max(F, wc);
-  if (w <= 64) return pool_bwd_dispatch<8>(rowptr_t, col_t, eperm, arg, dY, dX, n_src, F, ldarg, lddy, lddx, tdy, tdx, wc, st);
-  if (w <= 128) return pool_bwd_dispatch<16>(rowptr_t, col_t, eperm, arg, dY, dX, n_src, F, ldarg, lddy, lddx, tdy, tdx, wc, st);
-  if (w <= 256) return pool_bwd_dispatch<32>(rowptr_t, col_t, eperm, arg, dY, dX, n_src, F, ldarg, lddy, lddx, tdy, tdx, wc, st);
-  if (w <= 512) return pool_bwd_dispatch<64>(rowptr_t, col_t, eperm, arg, dY, dX, n_src, F, ldarg, lddy, lddx, tdy, tdx, wc, st);
-  return -1;
+  return for_slabs(F, std::max(ldy, lda), [&](int c0, int fc, int) {
+    const int wy = std::max(0, std::min(kSlab, ldy - c0));
+    const int wa = std::max(0, std::min(kSlab, lda - c0));
+    const void* x = in_at(X, t, c0, fc);
+    void* y = wy ? out_at(Y, t, c0) : Y;
+    int* a = arg && wa ? arg + c0 : nullptr;
+    return with_lanes(std::max({fc, wy, wa}), [&](auto l) {
+      constexpr int L = decltype(l)::value;
+      return with_type(t, [&](auto tt) {
+        constexpr int T = decltype(tt)::value;
+        hipLaunchKernelGGL((!is_min ? pool_fwd_kernel<L, T, false> : pool_fwd_kernel<L, T, true>),
+                           dim3(blocks(L, n_rows)), dim3(256), 0, st, rowptr, col, x, y, a, n_rows, fc, ldx, ldy, ldarg,
+                           wy, wa);
+        return (int)hipGetLastError();
+      });
+    });
+  });
 }
 
 // dX [n_src, lddx] from the forward's arg [n_dst, ldarg] and dY [n_dst, lddy]; padding
-// columns of dX are written 0.  Capturable like the forward.
+// columns of dX are written 0.  The (dY, dX) type pairs are gnn_launch_wspmm's.  Capturable
+// like the forward.
 extern "C" int gnn_launch_pool_bwd(const int* rowptr_t, const int* col_t, const int* eperm, const int* arg, int ldarg,
                                    const void* dY, int lddy, void* dX, int lddx, int n_src, int F, int tdy, int tdx,
                                    hipStream_t st) {
-  constexpr int slab = 512;
-  if (ldarg <= 0 || lddy <= 0 || lddx <= 0 || (ldarg % 8) || (lddy % 8) || (lddx % 8) || F < 0 || F > ldarg ||
-      F > lddy || F > lddx)
-    return -3;
-  if (!pool_pair_ok(tdy, tdx)) return -5;
+  if (F < 0 || !stride_ok(ldarg, F) || !stride_ok(lddy, F) || !stride_ok(lddx, F)) return -3;
+  if (!pair_ok(tdy, tdx)) return -5;
   if (n_src <= 0) return 0;
   if (!rowptr_t || !arg || !dY || !dX) return -3;
-  if (lddx <= slab)
-    return pool_bwd_launch(rowptr_t, col_t, eperm, arg, dY, dX, n_src, F, ldarg, lddy, lddx, tdy, tdx, lddx, st);
-  const size_t ys = tdy ? 2 : 4, xs = tdx ? 2 : 4;
-  for (int c0 = 0; c0 < lddx; c0 += slab) {
-    const int fc = std::max(0, std::min(slab, F - c0));
-    const int wc = std::min(slab, lddx - c0);
-    const int rc = pool_bwd_launch(rowptr_t, col_t, eperm, fc ? arg + c0 : arg, (const char*)dY + (fc ? c0 * ys : 0),
-                                   (char*)dX + c0 * xs, n_src, fc, ldarg, lddy, lddx, tdy, tdx, wc, st);
-    if (rc) return rc;
-  }
-  return 0;
+  return for_slabs(F, lddx, [&](int c0, int fc, int wc) {
+    const int* a = in_at(arg, c0, fc);
+    const void* dy = in_at(dY, tdy, c0, fc);
+    void* dx = out_at(dX, tdx, c0);
+    return with_lanes(std::max(fc, wc), [&](auto l) {
+      constexpr int L = decltype(l)::value;
+      return with_pair(tdy, tdx, [&](auto ty, auto tx) {
+        hipLaunchKernelGGL((pool_bwd_kernel<L, decltype(ty)::value, decltype(tx)::value>), dim3(blocks(L, n_src)),
+                           dim3(256), 0, st, rowptr_t, col_t, eperm, a, dy, dx, n_src, fc, ldarg, lddy, lddx, wc);
+        return (int)hipGetLastError();
+      });
+    });
+  });
 }

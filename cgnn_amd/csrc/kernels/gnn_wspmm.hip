@@ -8,7 +8,7 @@
 //                 e = (i, j) of the CSR: the gradient of the weighted aggregate with respect
 //                 to each edge value.
 //
-// Mapping (gnn_sparse.hip's): wave64, a sub-group of L lanes owns one row, each lane owns 8
+// Mapping (gnn_launch.h's): wave64, a sub-group of L lanes owns one row, each lane owns 8
 // consecutive features (one 16-byte load per gathered bf16 / fp16 row), L = 8 / 16 / 32 / 64
 // for widths up to 64 / 128 / 256 / 512; wider rows run as 512-column slabs in the
 // launchers.  The ids and values of a chunk of L edges come with one coalesced load per
@@ -27,10 +27,11 @@
 #include "cgnn_common.h"
 #include "cgnn_api.h"
 #include "gnn_gather.h"
-#include <algorithm>
+#include "gnn_launch.h"
 
 using namespace cgnn;
 using namespace cgnn::gather;
+using namespace cgnn::launch;
 
 namespace {
 
@@ -220,41 +221,7 @@ __global__ __launch_bounds__(256) void sddmm_kernel(
 }
 
 // ---------------------------------------------------------------- launchers
-template <int L>
-static int wspmm_dispatch(const int* rowptr, const int* col, const float* val, const int* eperm, const void* X,
-                          void* Y, const float* rs, const float* cs, const float* bias, int n_rows, int F, int ldx,
-                          int ldy, int xt, int yt, int relu, int wc, hipStream_t st) {
-  constexpr int RPB = 4 * (64 / L);               // rows per 256-thread block
-  dim3 grid((n_rows + RPB - 1) / RPB), block(256);
-#define CGNN_WSPMM(XT, YT)                                                                                  \
-  hipLaunchKernelGGL((wspmm_kernel<L, XT, YT>), grid, block, 0, st, rowptr, col, val, eperm, X, Y, rs, cs, \
-                     bias, n_rows, F, ldx, ldy, relu, wc)
-  // element-type codes: 0 fp32, 1 bf16, 2 fp16
-  if (xt == 1 && yt == 1) CGNN_WSPMM(1, 1);
-  else if (xt == 1 && yt == 0) CGNN_WSPMM(1, 0);
-  else if (xt == 2 && yt == 2) CGNN_WSPMM(2, 2);
-  else if (xt == 2 && yt == 0) CGNN_WSPMM(2, 0);
-  else if (xt == 0 && yt == 0) CGNN_WSPMM(0, 0);
-  else return -5;
-#undef CGNN_WSPMM
-  return (int)hipGetLastError();
-}
-
-static bool wspmm_pair_ok(int xt, int yt) {
-  return (xt == 1 && (yt == 1 || yt == 0)) || (xt == 2 && (yt == 2 || yt == 0)) || (xt == 0 && yt == 0);
-}
-
-// one launch writing output columns [0, wc) of its base (wc <= 512)
-static int wspmm_launch(const int* rowptr, const int* col, const float* val, const int* eperm, const void* X,
-                        void* Y, const float* rs, const float* cs, const float* bias, int n_rows, int F, int ldx,
-                        int ldy, int xt, int yt, int relu, int wc, hipStream_t st) {
-  const int w = std::max(F, wc);
-  if (w <= 64) return wspmm_dispatch<8>(rowptr, col, val, eperm, X, Y, rs, cs, bias, n_rows, F, ldx, ldy, xt, yt, relu, wc, st);
-  if (w <= 128) return wspmm_dispatch<16>(rowptr, col, val, eperm, X, Y, rs, cs, bias, n_rows, F, ldx, ldy, xt, yt, relu, wc, st);
-  if (w <= 256) return wspmm_dispatch<32>(rowptr, col, val, eperm, X, Y, rs, cs, bias, n_rows, F, ldx, ldy, xt, yt, relu, wc, st);
-  if (w <= 512) return wspmm_dispatch<64>(rowptr, col, val, eperm, X, Y, rs, cs, bias, n_rows, F, ldx, ldy, xt, yt, relu, wc, st);
-  return -1;
-}
+// (lane dispatch, grid, type tables and the slab walk: gnn_launch.h)
 
 // No allocation and no synchronisation: capturable into a hipGraph.  Return codes: see
 // cgnn_api.h.
@@ -262,64 +229,48 @@ extern "C" int gnn_launch_wspmm(const int* rowptr, const int* col, const float* 
                                 const void* X, void* Y, const float* rscale, const float* cscale,
                                 const float* bias, int n_rows, int F, int ldx, int ldy, int xt, int yt, int relu,
                                 hipStream_t st) {
-  constexpr int slab = 512;
-  if (ldx <= 0 || ldy <= 0 || (ldx % 8) || (ldy % 8) || F < 0 || F > ldx || F > ldy) return -3;
-  if (!wspmm_pair_ok(xt, yt)) return -5;
+  if (F < 0 || !stride_ok(ldx, F) || !stride_ok(ldy, F)) return -3;
+  if (!pair_ok(xt, yt)) return -5;
   if (n_rows <= 0) return 0;
-  if (ldy <= slab)
-    return wspmm_launch(rowptr, col, val, eperm, X, Y, rscale, cscale, bias, n_rows, F, ldx, ldy, xt, yt, relu, ldy,
-                        st);
-  // wide rows: column slabs of 512 output columns (16-byte aligned offsets), one launch
-  // each; the last slabs also write the padding columns up to ldy
-  const size_t xs = xt ? 2 : 4, ys = yt ? 2 : 4;
-  for (int c0 = 0; c0 < ldy; c0 += slab) {
-    const int fc = std::max(0, std::min(slab, F - c0));
-    const int wc = std::min(slab, ldy - c0);
-    const int rc = wspmm_launch(rowptr, col, val, eperm, (const char*)X + (fc ? c0 * xs : 0), (char*)Y + c0 * ys,
-                                rscale, cscale, bias && fc ? bias + c0 : nullptr, n_rows, fc, ldx, ldy, xt, yt,
-                                relu, wc, st);
-    if (rc) return rc;
-  }
-  return 0;
+  // one launch writing the columns [0, wc) of y, fc features among them
+  auto slab = [&](const void* x, void* y, const float* b, int fc, int wc) {
+    return with_lanes(std::max(fc, wc), [&](auto l) {
+      constexpr int L = decltype(l)::value;
+      return with_pair(xt, yt, [&](auto tx, auto ty) {
+        hipLaunchKernelGGL((wspmm_kernel<L, decltype(tx)::value, decltype(ty)::value>), dim3(blocks(L, n_rows)),
+                           dim3(256), 0, st, rowptr, col, val, eperm, x, y, rscale, cscale, b, n_rows, fc, ldx, ldy,
+                           relu, wc);
+        return (int)hipGetLastError();
+      });
+    });
+  };
+  // a row within one slab, apart from the walk: with F == 0 it keeps the caller's bias
+  // pointer, which the walk's padding-only rule would turn into null
+  if (ldy <= kSlab) return slab(X, Y, bias, F, ldy);
+  return for_slabs(F, ldy, [&](int c0, int fc, int wc) {
+    return slab(in_at(X, xt, c0, fc), out_at(Y, yt, c0), in_or_null(bias, c0, fc), fc, wc);
+  });
 }
 
-template <int L>
-static int sddmm_dispatch(const int* rowptr, const int* col, const void* A, const void* B, float* out,
-                          const float* rs, const float* cs, int n_rows, int F, int lda, int ldb, int t, int first,
-                          int last, hipStream_t st) {
-  constexpr int RPB = 4 * (64 / L);
-  dim3 grid((n_rows + RPB - 1) / RPB), block(256);
-#define CGNN_SDDMM(T)                                                                                         \
-  hipLaunchKernelGGL((sddmm_kernel<L, T>), grid, block, 0, st, rowptr, col, A, B, out, rs, cs, n_rows, F, lda, \
-                     ldb, first, last)
-  if (t == 0) CGNN_SDDMM(0);
-  else if (t == 1) CGNN_SDDMM(1);
-  else if (t == 2) CGNN_SDDMM(2);
-  else return -5;
-#undef CGNN_SDDMM
-  return (int)hipGetLastError();
-}
-
-// A and B share the storage type t.
+// A and B share the storage type t.  The feature slabs run in stream order; the kernel's
+// first / last turn them into one ordered sum per edge.
 extern "C" int gnn_launch_sddmm(const int* rowptr, const int* col, const void* A, const void* B, float* out,
                                 const float* rscale, const float* cscale, int n_rows, int F, int lda, int ldb,
                                 int t, hipStream_t st) {
-  constexpr int slab = 512;
-  if (lda <= 0 || ldb <= 0 || (lda % 8) || (ldb % 8) || F <= 0 || F > lda || F > ldb) return -3;
-  if (t < 0 || t > 2) return -5;
+  if (F <= 0 || !stride_ok(lda, F) || !stride_ok(ldb, F)) return -3;
+  if (!type_ok(t)) return -5;
   if (n_rows <= 0) return 0;
-  const size_t es = t ? 2 : 4;
-  for (int c0 = 0; c0 < F; c0 += slab) {
-    const int fc = std::min(slab, F - c0);
-    const void* a = (const char*)A + c0 * es;
-    const void* b = (const char*)B + c0 * es;
-    const int first = c0 == 0, last = c0 + slab >= F;
-    int rc;
-    if (fc <= 64) rc = sddmm_dispatch<8>(rowptr, col, a, b, out, rscale, cscale, n_rows, fc, lda, ldb, t, first, last, st);
-    else if (fc <= 128) rc = sddmm_dispatch<16>(rowptr, col, a, b, out, rscale, cscale, n_rows, fc, lda, ldb, t, first, last, st);
-    else if (fc <= 256) rc = sddmm_dispatch<32>(rowptr, col, a, b, out, rscale, cscale, n_rows, fc, lda, ldb, t, first, last, st);
-    else rc = sddmm_dispatch<64>(rowptr, col, a, b, out, rscale, cscale, n_rows, fc, lda, ldb, t, first, last, st);
-    if (rc) return rc;
-  }
-  return 0;
+  return for_slabs(F, F, [&](int c0, int fc, int) {
+    const void* a = in_at(A, t, c0, fc);
+    const void* b = in_at(B, t, c0, fc);
+    const int first = c0 == 0, last = c0 + kSlab >= F;
+    return with_lanes(fc, [&](auto l) {
+      constexpr int L = decltype(l)::value;
+      return with_type(t, [&](auto tt) {
+        hipLaunchKernelGGL((sddmm_kernel<L, decltype(tt)::value>), dim3(blocks(L, n_rows)), dim3(256), 0, st, rowptr,
+                           col, a, b, out, rscale, cscale, n_rows, fc, lda, ldb, first, last);
+        return (int)hipGetLastError();
+      });
+    });
+  });
 }

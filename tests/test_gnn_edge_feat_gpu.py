@@ -234,6 +234,62 @@ def test_egrad_exact_over_row_lengths_widths_and_dtypes(F, ld, L):
                 assert torch.all(dv2.cpu()[nnz:] == SENT)
 
 
+# ------------------------------------------------------------------ 2b. past the second slab
+@functools.lru_cache(maxsize=None)
+def _small_graph():
+    """9 rows, 40 edges, one row empty."""
+    rng = np.random.default_rng(45)
+    rp, col, val = _csr([3, 0, 1, 9, 4, 5, 7, 9, 2], N_SRC, rng)
+    assert col.numel() == 40
+    return dict(n=9, nnz=40, rp=rp, col=col, val=val, rows=_rows(rp), rp_d=rp.to(DEV), col_d=col.to(DEV),
+                val_d=val.to(DEV))
+
+
+# (F, ld of X / E / Y / dY, ld of dE).  (1030, 1032): a third 512-column slab holding 6
+# features and 2 padding columns, dval the ordered sum of three launches; (500, 1032): slabs
+# two and three hold padding only; (8, 8, 520): a second slab that writes 8 padding columns
+# of dE and no dval
+@pytest.mark.parametrize("F,ld,ldde", [(1030, 1032, 1032), (500, 1032, 1032), (8, 8, 520)])
+def test_espmm_and_egrad_exact_past_the_second_slab(F, ld, ldde):
+    g = _small_graph()
+    n, nnz = g["n"], g["nnz"]
+    rng = np.random.default_rng(4200 + F)
+    X = torch.full((N_SRC, ld), PAD, dtype=F64)
+    E = torch.full((nnz, ld), PAD, dtype=F64)
+    G = torch.full((n, ld), PAD, dtype=F64)
+    X[:, :F], E[:, :F], G[:, :F] = _ints(rng, -3, 3, (N_SRC, F)), _ints(rng, -3, 3, (nnz, F)), _ints(rng, -3, 3, (n, F))
+    gy, w = G[g["rows"], :F], g["val"].double()[:, None]
+    for case in CASES:
+        op, relu, with_x = case
+        m, d = _messages(g, X, E, F, case)
+        ref, ref_dv, ref_de = _segsum(g, m * w), (gy * m).sum(1), gy * d * w
+        # 9 edges of |w m| <= 18 per row; |dY m| <= 27 per feature; |w dY d| <= 18 in quarter units
+        assert _exact(ref, 8192) and _exact(ref_dv, 27 * 1032) and _exact(ref_de, 18.25)
+        for dt in DTYPES:
+            Xd = X.to(dt).to(DEV) if with_x else None
+            Ed, Gd = E.to(dt).to(DEV), G.to(dt).to(DEV)
+            kw = dict(op=op, relu=relu, val=g["val_d"])
+            what = "%s relu=%d X=%d %s F=%d ldde=%d" % (op, relu, with_x, dt, F, ldde)
+            exp = torch.zeros(n, ld, dtype=F64)
+            exp[:, :F] = ref
+            full = torch.full((n + 3, ld), SENT, dtype=dt, device=DEV)
+            ops.espmm(g["rp_d"], g["col_d"], Xd, Ed, F, out=full[:n], **kw)
+            got = full.cpu()
+            _assert_same(got[:n], exp.to(dt), what)
+            assert torch.all(got[:n, F:] == 0), what + ": padding columns"
+            assert torch.all(got[n:] == SENT), what + ": written past the last row's stride"
+            exp_de = torch.zeros(nnz, ldde, dtype=F64)
+            exp_de[:, :F] = ref_de
+            de = torch.full((nnz + 3, ldde), SENT, dtype=dt, device=DEV)
+            dv = torch.full((nnz + 5,), SENT, device=DEV)
+            ops.egrad(g["rp_d"], g["col_d"], Gd, Xd, Ed, F, dE=de[:nnz], dval=dv[:nnz], **kw)
+            got_de, got_dv = de.cpu(), dv.cpu()
+            _assert_same(got_de[:nnz], exp_de.to(dt), what + " dE")
+            _assert_same(got_dv[:nnz], ref_dv.float(), what + " dval")
+            assert torch.all(got_de[:nnz, F:] == 0), what + ": dE padding columns"
+            assert torch.all(got_de[nnz:] == SENT) and torch.all(got_dv[nnz:] == SENT), what + ": tail written"
+
+
 # ------------------------------------------------------------------ 3. transposed dx pass
 def test_transposed_pass_is_the_gradient_with_respect_to_the_node_rows():
     """On the rectangular 53 x 257 graph: espmm mul over ``transposed_perm()`` with X = dY

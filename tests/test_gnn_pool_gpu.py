@@ -293,6 +293,60 @@ def test_pool_backward_exact_over_row_lengths_widths_and_dtypes(F, ld, L):
         assert torch.all(got[NEVER] == 0), what + ": a source never selected"
 
 
+# ------------------------------------------------------------------ 4b. past the second slab
+@functools.lru_cache(maxsize=None)
+def _small_graph():
+    """9 rows over 9 sources, 40 edges, one row empty; with its transpose."""
+    rng = np.random.default_rng(43)
+    deg = [3, 0, 1, 9, 4, 5, 7, 9, 2]
+    rp, col = _csr(deg, 9, rng)
+    assert col.size == 40
+    rp_t, col_t, eperm = transpose_csr(torch.from_numpy(rp), torch.from_numpy(col), 9, with_perm=True)
+    return dict(n=9, rp=rp, col=col, rp_d=torch.from_numpy(rp).to(DEV), col_d=torch.from_numpy(col).to(DEV),
+                t=(rp_t.to(DEV), col_t.to(DEV), eperm.to(DEV)))
+
+
+# (F, ld of X / Y / dY / dX, ld of arg).  (1030, 1032): a third 512-column slab holding 6
+# features and 2 padding columns; (500, 1032): slabs two and three hold padding only;
+# (8, 8, 520): a second slab that writes 8 padding columns of arg and nothing of Y
+@pytest.mark.parametrize("F,ld,ldarg", [(1030, 1032, 1032), (500, 1032, 1032), (8, 8, 520)])
+def test_pool_forward_and_backward_exact_past_the_second_slab(F, ld, ldarg):
+    g = _small_graph()
+    n, rp, col = g["n"], g["rp"], g["col"]
+    Xd = _features("ties", F, ld, 7000 + F, n=n)
+    A_max = None
+    for dt in (F32, BF16, F16):
+        Xs = Xd.to(dt)
+        for reduce in ("max", "min"):
+            Yr, Ar = _pool_ref(rp, col, Xs.double().numpy(), F, reduce == "min")
+            ofull = torch.full((n + 3, ld), SENT, dtype=dt, device=DEV)
+            afull = torch.full((n + 3, ldarg), SENT, dtype=torch.int32, device=DEV)
+            ops.pool(g["rp_d"], g["col_d"], Xs.to(DEV), F, reduce=reduce, out=ofull[:n], arg=afull[:n])
+            got, garg = ofull.cpu(), afull.cpu()
+            what = "%s %s F=%d ldarg=%d" % (dt, reduce, F, ldarg)
+            _assert_same(got[:n, :F], torch.from_numpy(Yr), what)
+            assert torch.equal(garg[:n, :F].long(), torch.from_numpy(Ar)), what + ": arg"
+            assert torch.all(got[:n, F:] == 0) and torch.all(garg[:n, F:] == -1), what + ": padding columns"
+            assert torch.all(got[1] == 0) and torch.all(garg[1] == -1), what + ": the empty row"
+            assert torch.all(got[n:] == SENT) and torch.all(garg[n:] == SENT), what + ": past the last row's stride"
+            if dt == F32 and reduce == "max":
+                A_max, Ar_max = afull[:n], Ar
+    rng = np.random.default_rng(7100 + F)
+    dYd = torch.full((n, ld), BIG, dtype=F64)
+    dYd[:, :F] = torch.from_numpy(rng.integers(-3, 4, (n, F)).astype(np.float64))
+    ref = torch.from_numpy(_pool_bwd_ref(rp, col, Ar_max, dYd.numpy(), n, F))
+    assert torch.equal(ref.float().double(), ref) and float(ref.abs().max()) <= 3 * 40 and float(ref.abs().sum()) > 0
+    rp_t, col_t, eperm = g["t"]
+    for ydt, xdt in PAIRS:
+        full = torch.full((n + 3, ld), SENT, dtype=xdt, device=DEV)
+        ops.pool_bwd(rp_t, col_t, eperm, A_max, dYd.to(ydt).to(DEV), F, out=full[:n])
+        got = full.cpu()
+        what = "pool_bwd %s->%s F=%d ldarg=%d" % (ydt, xdt, F, ldarg)
+        _assert_same(got[:n, :F], ref.to(xdt), what)
+        assert torch.all(got[:n, F:] == 0), what + ": padding columns"
+        assert torch.all(got[n:] == SENT), what + ": past the last row's stride"
+
+
 # ------------------------------------------------------------------ 5. duplicate edges
 def test_duplicate_edges_are_not_double_counted():
     """A row lists source 1 three times (equal values, so the first edge wins the tie): the

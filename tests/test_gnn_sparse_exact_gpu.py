@@ -161,6 +161,48 @@ def test_spmm_exact_over_row_lengths_and_dtypes(F, ld, L):
                 assert torch.all(got[n:] == SENT), what + ": rows past n_rows written"
 
 
+# (1030, 1032): a third 512-column slab holding 6 features, the ones column and one padding
+# column; (500, 1032): slabs two and three hold padding only, the ones column in the third
+@pytest.mark.parametrize("F,ld,unit_col", [(1030, 1032, 1030), (500, 1032, 1030)])
+def test_spmm_exact_past_the_second_slab(F, ld, unit_col):
+    """9 rows, 40 edges: every dtype pair, both kernels, the epilogue with everything on and
+    with everything off; zero padding columns, and nothing written past the last row."""
+    rng = np.random.default_rng(1500 + F)
+    rp, col = _csr([3, 0, 1, 9, 4, 5, 7, 9, 2], N_SRC, rng)
+    n, A = 9, _count_matrix(rp, col, N_SRC)
+    assert col.numel() == 40
+    rs, cs = _pow2(rng, n), _pow2(rng, N_SRC)
+    Xd = torch.zeros(N_SRC, ld, dtype=F64)
+    Xd[:, :F] = _ints(rng, -3, 3, (N_SRC, F))
+    bias = _ints(rng, -2, 2, (F,))
+    init_rows = n - 2
+    init = torch.zeros(init_rows, ld, dtype=F64)
+    init[:, :F] = _ints(rng, -4, 4, (init_rows, F))
+    agg = {False: A @ Xd[:, :F], True: A @ (cs[:, None] * Xd[:, :F])}
+    rp_d, col_d, rs_d, cs_d = rp.to(DEV), col.to(DEV), rs.float().to(DEV), cs.float().to(DEV)
+    bias_d, init_d = bias.float().to(DEV), init.float().to(DEV)
+    for xdt, ydt, use_cs in SPMM_PAIRS:
+        X = Xd.to(xdt).to(DEV)
+        for on in (False, True):
+            ref = agg[use_cs].clone()
+            if on:
+                ref[:init_rows] += init[:, :F]
+                ref = (ref * rs[:, None] + bias).clamp_min(0)
+            assert _fp32_exact(ref) and float(ref.abs().max()) < 4096
+            exp = torch.zeros(n, ld, dtype=F64)
+            exp[:, :F] = ref
+            exp[:, unit_col] = 1
+            for short in (False, True):
+                full = torch.full((n + 3, ld), SENT, dtype=ydt, device=DEV)
+                ops.spmm(rp_d, col_d, X, F, rscale=rs_d if on else None, bias=bias_d if on else None, relu=on,
+                         out=full[:n], unit_col=unit_col, init=init_d if on else None,
+                         init_rows=init_rows if on else None, cscale=cs_d if use_cs else None, short_rows=short)
+                got = full.cpu()
+                what = "%s->%s cs=%d epilogue=%d short=%d F=%d" % (xdt, ydt, use_cs, on, short, F)
+                _assert_same(got[:n], exp.to(ydt), what)
+                assert torch.all(got[n:] == SENT), what + ": written past the last row's stride"
+
+
 def test_spmm_mixed_pair_with_column_scale_raises():
     """A column scale is compiled for the same-type pairs only: the launcher's code -5."""
     g = _spmm_graph(8)

@@ -229,6 +229,56 @@ def test_sddmm_exact_over_row_lengths_widths_and_dtypes(F, ld, L):
                 assert torch.all(got[e0:e1] == got[e0]), what + ": duplicate edges differ"
 
 
+# ------------------------------------------------------------------ 4b. past the second slab
+@functools.lru_cache(maxsize=None)
+def _small_graph():
+    """9 rows, 40 edges, one row empty."""
+    rng = np.random.default_rng(41)
+    deg = [3, 0, 1, 9, 4, 5, 7, 9, 2]
+    rp, col, val = _csr(deg, N_SRC, rng)
+    assert col.numel() == 40
+    return dict(n=len(deg), rp=rp, col=col, val=val, rp_d=rp.to(DEV), col_d=col.to(DEV), val_d=val.to(DEV),
+                A=_dense(rp, col, val, N_SRC), rs=_pow2(rng, len(deg)), cs=_pow2(rng, N_SRC))
+
+
+# (1030, 1032): a third 512-column slab holding 6 features and 2 padding columns;
+# (500, 1032): slabs two and three hold padding only, the third is 8 columns wide
+@pytest.mark.parametrize("F,ld", [(1030, 1032), (500, 1032)])
+def test_wspmm_and_sddmm_exact_past_the_second_slab(F, ld):
+    g = _small_graph()
+    n, nnz = g["n"], g["col"].numel()
+    Xd, bias = _features(F, ld, 4000 + F)
+    rs_d, cs_d, bias_d = g["rs"].float().to(DEV), g["cs"].float().to(DEV), bias.float().to(DEV)
+    for xdt, ydt in PAIRS:
+        X = Xd.to(xdt).to(DEV)
+        for cfg in (CONFIGS[0], CONFIGS[1]):
+            use_rs, use_cs, use_bias, relu = cfg
+            exp = torch.zeros(n, ld, dtype=F64)
+            exp[:, :F] = _wspmm_ref(g, Xd, bias, F, cfg)
+            full = torch.full((n + 3, ld), SENT, dtype=ydt, device=DEV)
+            ops.wspmm(g["rp_d"], g["col_d"], g["val_d"], X, F, rscale=rs_d if use_rs else None,
+                      cscale=cs_d if use_cs else None, bias=bias_d if use_bias else None, relu=relu, out=full[:n])
+            got = full.cpu()
+            what = "%s->%s F=%d epilogue=%d" % (xdt, ydt, F, use_rs)
+            _assert_same(got[:n], exp.to(ydt), what)
+            assert torch.all(got[:n, F:] == 0), what + ": padding columns"
+            assert torch.all(got[n:] == SENT), what + ": written past the last row's stride"
+    rng = np.random.default_rng(4100 + F)
+    Ad = torch.full((n, ld), 5.0, dtype=F64)
+    Bd = torch.full((N_SRC, ld), 5.0, dtype=F64)
+    Ad[:, :F] = _ints(rng, -3, 3, (n, F))
+    Bd[:, :F] = _ints(rng, -3, 3, (N_SRC, F))
+    rows, colj = _rows(g["rp"]), g["col"].long()
+    ref = (Ad[:, :F] @ Bd[:, :F].t())[rows, colj] * g["rs"][rows] * g["cs"][colj]
+    assert _exact(ref, 9 * 1032 * 4 + 1)
+    for dt in (F32, BF16, F16):
+        out = torch.full((nnz + 5,), SENT, device=DEV)
+        ops.sddmm(g["rp_d"], g["col_d"], Ad.to(dt).to(DEV), Bd.to(dt).to(DEV), F, rscale=rs_d, cscale=cs_d, out=out)
+        got = out.cpu()
+        _assert_same(got[:nnz], ref.float(), "sddmm %s F=%d" % (dt, F))
+        assert torch.all(got[nnz:] == SENT), "sddmm: tail past nnz written"
+
+
 # ------------------------------------------------------------------ 5. edge cases
 def test_graph_with_rows_but_no_edges():
     n, F = 9, 24
