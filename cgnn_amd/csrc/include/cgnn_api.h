@@ -250,6 +250,10 @@ int gnn_launch_halo_rows(const void* src, long src_pitch, const long* src_idx, v
 
 // ---- gnn_sampler.hip: neighbour sampling, the mini-batch pipeline and its worker thread.
 // The per-level arguments (int* const* and friends) are host arrays of L device pointers.
+// Both launchers refuse before their first HIP call (tests/test_sampler_exact_cpu.py):
+// sample_neighbors returns -3 for fanout > 64, and only then 0 for n <= 0 (a fanout < 0
+// copies whole rows); sample_blocks returns -3 unless L >= 1, n >= 1, every fan[l] in
+// 1..64, every nd_max[l] >= 1 and 0 <= n_seeds <= nd_max[0], with nothing enqueued.
 int gnn_launch_sample_neighbors(const int* rowptr, const int* col, const int* nodes, int n, int fanout,
                                 const int* out_ptr, int* out_col, uint32_t k0, uint32_t k1, uint32_t salt,
                                 hipStream_t st);

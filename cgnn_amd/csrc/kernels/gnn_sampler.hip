@@ -63,16 +63,15 @@ __global__ __launch_bounds__(256) void sample_neighbors_kernel(
 extern "C" int gnn_launch_sample_neighbors(const int* rowptr, const int* col, const int* nodes, int n, int fanout,
                                            const int* out_ptr, int* out_col, uint32_t k0, uint32_t k1,
                                            uint32_t salt, hipStream_t st) {
+  if (fanout > 64) return -3;          // before the zero-row return (cgnn_api.h)
   if (n <= 0) return 0;
   dim3 grid((n + 255) / 256), block(256);
   if (fanout <= 16)
     hipLaunchKernelGGL((sample_neighbors_kernel<16>), grid, block, 0, st, rowptr, col, nodes, n, fanout, out_ptr,
                        out_col, k0, k1, salt, (const int*)nullptr, (uint8_t*)nullptr);
-  else if (fanout <= 64)
+  else
     hipLaunchKernelGGL((sample_neighbors_kernel<64>), grid, block, 0, st, rowptr, col, nodes, n, fanout, out_ptr,
                        out_col, k0, k1, salt, (const int*)nullptr, (uint8_t*)nullptr);
-  else
-    return -3;
   return (int)hipGetLastError();
 }
 
@@ -320,13 +319,32 @@ __global__ void sb_publish_kernel(const int* __restrict__ counts, int* __restric
 
 static unsigned blocks_for(long n, int t = 256) { return (unsigned)std::max(1L, (n + t - 1) / t); }
 
+// Layout of the pipeline's int32 scratch (bscratch): the flag-scan block counts (nb used of
+// 2 nb + 2), then the scan block sums (sbmax used of 2 sbmax), then the scan values (vmax).
+// vmax bounds every scan's length + 1: a level's destinations are the seeds or the previous
+// level's sources, its sources at most min(nd_max (fan + 1), n).
+namespace {
+struct SbLayout {
+  long nb, vmax, sbmax;
+  long sbsum() const { return 2 * nb + 2; }
+  long svals() const { return sbsum() + 2 * sbmax; }
+  long size() const { return svals() + vmax; }
+};
+
+SbLayout sb_layout(int n, int L, const int* fan, const int* nd_max) {
+  SbLayout y;
+  y.nb = ((long)n + FLAG_BLK - 1) / FLAG_BLK;
+  y.vmax = 1;
+  for (int l = 0; l < L; ++l)
+    y.vmax = std::max(y.vmax, std::min<long>((long)nd_max[l] * (fan[l] + 1), (long)n) + 1);
+  y.sbmax = (y.vmax + SB - 1) / SB + 1;
+  return y;
+}
+}  // namespace
+
 // int32 scratch the pipeline needs (bscratch argument of gnn_launch_sample_blocks)
 extern "C" long gnn_sample_blocks_scratch(int n, int L, const int* fan, const int* nd_max) {
-  const long nb = (n + FLAG_BLK - 1) / FLAG_BLK;
-  long vmax = 1;
-  for (int l = 0; l < L; ++l) vmax = std::max(vmax, std::min<long>((long)nd_max[l] * (fan[l] + 1), (long)n) + 1);
-  const long sbmax = (vmax + SB - 1) / SB + 1;
-  return 2 * nb + 2 + 2 * sbmax + vmax;
+  return sb_layout(n, L, fan, nd_max).size();
 }
 
 // bytes of the pipeline's flag array for n ids: whole 4096-id blocks (the flag passes
@@ -346,16 +364,17 @@ extern "C" int gnn_launch_sample_blocks(const int* rowptr, const int* col, int n
                                         int* const* src, int* const* rp_t, int* const* col_t, int* const* cnt_t,
                                         int* counts, uint8_t* flag, int* map, int* bscratch, uint32_t k0,
                                         uint32_t k1, uint32_t salt, hipStream_t st, int* counts_host) {
-  const int nb = (n + FLAG_BLK - 1) / FLAG_BLK;
-  // scan scratch after the flag-scan counts: block sums, block offsets, values
-  long vmax = 1;
-  for (int l = 0; l < L; ++l) vmax = std::max(vmax, std::min<long>((long)nd_max[l] * (fan[l] + 1), (long)n) + 1);
-  const long sbmax = (vmax + SB - 1) / SB + 1;
-  int* sbsum = bscratch + 2 * nb + 2;
-  int* svals = sbsum + 2 * sbmax;
+  // every refusal comes before the first launch: nothing is enqueued, no device is needed
+  if (L < 1 || n < 1) return -3;
+  for (int l = 0; l < L; ++l)
+    if (fan[l] < 1 || fan[l] > 64 || nd_max[l] < 1) return -3;
+  if (n_seeds < 0 || n_seeds > nd_max[0]) return -3;
+  const SbLayout lay = sb_layout(n, L, fan, nd_max);
+  const int nb = (int)lay.nb;
+  int* sbsum = bscratch + lay.sbsum();
+  int* svals = bscratch + lay.svals();
   for (int l = 0; l < L; ++l) {
     const int fo = fan[l];
-    if (fo < 1 || fo > 64) return -3;
     const int* nodes = l == 0 ? seeds : src[l - 1];
     const int* nd_dev = l == 0 ? nullptr : counts + 2 * (l - 1);
     const int ndh = l == 0 ? n_seeds : 0;
