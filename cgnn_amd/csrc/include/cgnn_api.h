@@ -160,6 +160,21 @@ int gnn_launch_pool_bwd(const int* rowptr_t, const int* col_t, const int* eperm,
                         const void* dY, int lddy, void* dX, int lddx, int n_src, int F, int tdy, int tdx,
                         hipStream_t st);
 
+// ---- gnn_readout.hip: reduction of contiguous row segments (the node rows of each graph of
+// a batch) and its reverse, a segment row broadcast to the segment's rows.  ptr: int32
+// [S + 1]; op: 0 sum (rscale fp32 [S] or null; the seven pairs (tin, tout) of wspmm plus
+// fp32 -> bf16 / fp16), 1 max, 2 min (tin == tout; arg int32 [S, ldarg] or null = the row
+// that supplied the value, or arg_in[row] with arg_in).  seg_id: int32 [n]; with arg the
+// broadcast writes U[s] where arg[s] names the row and 0 elsewhere.  Checks in this order:
+// -3 a bad stride, -5 a type pair that is not compiled, 0 without a launch for S <= 0 /
+// n <= 0, -3 a required pointer missing (X may be null when every segment is empty), -1 an
+// op outside 0..2
+int gnn_launch_seg_reduce(const int* ptr, const void* X, void* Y, const float* rscale, const int* arg_in, int* arg,
+                          int S, int F, int ldx, int ldy, int ldarg_in, int ldarg, int tin, int tout, int op,
+                          hipStream_t st);
+int gnn_launch_seg_bcast(const int* seg_id, const void* U, const float* rscale, const int* arg, void* out, int n,
+                         int F, int ldu, int ldarg, int ldo, int tin, int tout, hipStream_t st);
+
 // ---- gnn_edge_softmax.hip: softmax over each row's edges and its gradient.  s / p / dp / ds
 // are fp32, head-major [K, ld] (head k's edge e at k * ld + e); p may alias s and ds may
 // alias dp.  lanes: the sub-group width, 0 = from nnz / n_rows.  -3: a required pointer

@@ -246,6 +246,24 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("rowptr_t"), py::arg("col_t"), py::arg("eperm"), py::arg("arg"), py::arg("ld_arg"), py::arg("dy"),
      py::arg("ld_dy"), py::arg("dx"), py::arg("ld_dx"), py::arg("n_src"), py::arg("F"), py::arg("dy_type"),
      py::arg("dx_type"), py::arg("st"));
+  // graph-level readout: segment reduction and broadcast (gnn_readout.hip)
+  m.def("gnn_seg_reduce", [](uint64_t ptr, uint64_t x, uint64_t y, uint64_t rscale, uint64_t arg_in, uint64_t arg,
+                             int n_seg, int F, int ld_x, int ld_y, int ld_arg_in, int ld_arg, int x_type, int y_type,
+                             int op, uint64_t st) {
+    chk(gnn_launch_seg_reduce(Pt<const int>(ptr), Pt<const void>(x), Pt<void>(y), Pt<const float>(rscale),
+                              Pt<const int>(arg_in), Pt<int>(arg), n_seg, F, ld_x, ld_y, ld_arg_in, ld_arg, x_type,
+                              y_type, op, S(st)),
+        "gnn_seg_reduce");
+  }, py::arg("ptr"), py::arg("x"), py::arg("y"), py::arg("rscale"), py::arg("arg_in"), py::arg("arg"),
+     py::arg("n_seg"), py::arg("F"), py::arg("ld_x"), py::arg("ld_y"), py::arg("ld_arg_in"), py::arg("ld_arg"),
+     py::arg("x_type"), py::arg("y_type"), py::arg("op"), py::arg("st"));
+  m.def("gnn_seg_bcast", [](uint64_t seg_id, uint64_t u, uint64_t rscale, uint64_t arg, uint64_t out, int n, int F,
+                            int ld_u, int ld_arg, int ld_out, int u_type, int out_type, uint64_t st) {
+    chk(gnn_launch_seg_bcast(Pt<const int>(seg_id), Pt<const void>(u), Pt<const float>(rscale), Pt<const int>(arg),
+                             Pt<void>(out), n, F, ld_u, ld_arg, ld_out, u_type, out_type, S(st)),
+        "gnn_seg_bcast");
+  }, py::arg("seg_id"), py::arg("u"), py::arg("rscale"), py::arg("arg"), py::arg("out"), py::arg("n"), py::arg("F"),
+     py::arg("ld_u"), py::arg("ld_arg"), py::arg("ld_out"), py::arg("u_type"), py::arg("out_type"), py::arg("st"));
   // softmax over each row's edges and its gradient (gnn_edge_softmax.hip)
   m.def("gnn_edge_softmax_fwd", [](uint64_t rowptr, uint64_t s, uint64_t p, int n_rows, int nnz, int K, long ld,
                                    float scale, int lanes, uint64_t st) {

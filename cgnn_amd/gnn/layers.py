@@ -24,6 +24,9 @@ track, not in the reference.
   the node rows, the edge rows (``ops.egrad``) and optional per-edge weights; GIN with edge
   features and SchNet's continuous-filter convolution built on it.
 
+The step these models end in -- one row per graph of a batch of graphs -- is in
+``gnn/readout.py`` (``GraphBatch``, ``graph_readout``, ``graph_broadcast``, ``GlobalAttention``).
+
 Everything runs on the same ``ops.spmm`` as the fused 2-layer trainer (HIP on
 GPU tensors, PyTorch index ops on CPU tensors); dense products are hipBLASLt
 GEMMs.  Storage dtype follows the input (fp32 / bf16 / fp16); aggregation

@@ -4,7 +4,8 @@ The CPU branch is the numerical reference used by the tests (and lets the
 models run in CI); on a GPU the HIP kernels of csrc/kernels/gnn_sparse.hip (and
 gnn_wspmm.hip for the edge-weighted ops, gnn_pool.hip for max / min pooling,
 gnn_edge_softmax.hip for the softmax over a node's edges, gnn_espmm.hip for the aggregate
-with a feature row per edge) are mandatory -- a missing extension raises instead of silently falling back.
+with a feature row per edge, gnn_readout.hip for the reduction of each graph's node rows
+and its reverse) are mandatory -- a missing extension raises instead of silently falling back.
 """
 from __future__ import annotations
 
@@ -471,6 +472,161 @@ def pool_bwd(rowptr_t, col_t, eperm, arg, dY, F, out=None, out_dtype=None, ld_ou
         acc[r] += torch.where(arg[i, :F].long() == e[:, None], dY[i, :F].to(at), torch.zeros((), dtype=at))
     out[:n_src].zero_()
     out[:n_src, :F] = acc.to(out.dtype)
+    return out
+
+
+# rows per chunk of the two-level graph readout (gnn/readout.py).  512: the fastest of 64 / 256 /
+# 512 / 1024 on 4 graphs of 250 k nodes (docs/PERF.md, "Graph readout"); graphs of at most one
+# chunk run as a single launch
+READOUT_CHUNK = 512
+
+_SEG_OPS = {"sum": 0, "max": 1, "min": 2}
+
+
+def _check_ptr(ptr, n_rows, what):
+    if ptr.dim() != 1 or ptr.numel() < 1:
+        raise ValueError("CGNN_CHECK: %s: ptr must be a non-empty vector" % what)
+    p = ptr.long()
+    if int(p[0]) != 0 or bool((p[1:] < p[:-1]).any()):
+        raise ValueError("CGNN_CHECK: %s: ptr must start at 0 and never decrease" % what)
+    if int(p[-1]) > n_rows:
+        raise ValueError("CGNN_CHECK: %s: ptr ends at %d but the input has %d rows" % (what, int(p[-1]), n_rows))
+
+
+def _seg_gpu_operands(what, ints, floats, dense):
+    """TypeError / ValueError for GPU operands that are not int32 (``ints``), not fp32
+    (``floats``) or not contiguous (all of them and ``dense``); None entries are skipped."""
+    for name, t in ints:
+        if t is not None and t.dtype != torch.int32:
+            raise TypeError("%s: %s must be int32, got %s" % (what, name, t.dtype))
+    for name, t in floats:
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("%s: %s must be fp32, got %s" % (what, name, t.dtype))
+    for name, t in tuple(ints) + tuple(floats) + tuple(dense):
+        if t is not None and not t.is_contiguous():
+            raise ValueError("%s: contiguous operands expected (%s)" % (what, name))
+
+
+def seg_reduce(ptr, X, F, reduce="sum", rscale=None, arg_in=None, out=None, arg=None, with_arg=False, out_dtype=None,
+               ld_out=None):
+    """Reduction of contiguous row segments (gnn_readout.hip, seg_reduce_kernel): output row
+    ``s`` reduces the rows ``ptr[s] .. ptr[s+1] - 1`` of ``X`` ``[*, ldx]``; ``ptr`` is int32
+    ``[S + 1]``, starts at 0 and never decreases.  Returns ``(Y, arg)``.
+
+    ``reduce="sum"``: ``Y[s,f] = rscale[s] * sum_i X[i,f]``, accumulated in fp32 in an order
+    that depends on the segment's length alone, one product (``rscale`` fp32 ``[S]``, default
+    1) and one rounding to ``out_dtype`` (default X's; the GPU compiles the pairs of ``wspmm``
+    and fp32 -> bf16 / fp16); ``arg`` is None.  ``"max"`` / ``"min"``: the scan rule of ``pool``
+    -- ties go to the first row holding the value, a NaN propagates -- Y in X's type, and
+    ``arg[s,f]`` (with ``with_arg`` or an ``arg`` buffer; int32) the row index ``i`` that
+    supplied it, or ``arg_in[i,f]`` with ``arg_in`` (int32 ``[*, ld]``): a second pass over
+    partial results hands the first pass's indices through.  An empty segment and the padding
+    columns ``F <= f < ld`` give ``Y = 0``, ``arg = -1``.  No atomics: bit-identical from run
+    to run, and a segment's result does not depend on where it stands.  CPU tensors: PyTorch,
+    fp32 accumulation (fp64 for fp64 inputs)."""
+    if reduce not in _SEG_OPS:
+        raise ValueError("seg_reduce: reduce must be 'sum', 'max' or 'min', got %r" % (reduce,))
+    is_sum = reduce == "sum"
+    if is_sum and (arg is not None or arg_in is not None or with_arg):
+        raise ValueError("seg_reduce: the sum has no arg")
+    if not is_sum and rscale is not None:
+        raise ValueError("seg_reduce: rscale goes with reduce='sum' only")
+    S = ptr.numel() - 1
+    if out is None:
+        out = torch.empty(S, ld_out or X.shape[1], dtype=(out_dtype or X.dtype) if is_sum else X.dtype,
+                          device=X.device)
+    if not is_sum and out.dtype != X.dtype:
+        raise TypeError("seg_reduce: max / min give the input's dtype, got %s for %s" % (out.dtype, X.dtype))
+    if arg is None and with_arg:
+        arg = torch.empty(S, out.shape[1], dtype=torch.int32, device=X.device)
+    if checks.enabled():
+        _check_ptr(ptr, X.shape[0], "seg_reduce")
+        checks.rows(out, S, "seg_reduce out")
+        checks.rows(rscale, S, "seg_reduce rscale")
+        if arg is not None:
+            _check_arg(arg, S, F, "seg_reduce")
+        if arg_in is not None:
+            _check_arg(arg_in, int(ptr[-1]), F, "seg_reduce arg_in")
+    if X.is_cuda:
+        _seg_gpu_operands("seg_reduce", (("ptr", ptr), ("arg", arg), ("arg_in", arg_in)), (("rscale", rscale),),
+                          (("X", X), ("out", out)))
+        native.hip().gnn_seg_reduce(ptr.data_ptr(), X.data_ptr(), out.data_ptr(), _ptr(rscale), _ptr(arg_in),
+                                    _ptr(arg), S, F, X.shape[1], out.shape[1],
+                                    arg_in.shape[1] if arg_in is not None else 0,
+                                    arg.shape[1] if arg is not None else 0, dtype_code(X.dtype),
+                                    dtype_code(out.dtype), _SEG_OPS[reduce], _st(X))
+        return out, arg
+    at = _acc_dtype(X.dtype)
+    p = ptr.long()
+    cnt = p[1:] - p[:-1]
+    if is_sum:
+        rows = _row_ids(ptr)
+        acc = torch.zeros(S, F, dtype=at).index_add_(0, rows, X[:rows.numel(), :F].to(at))
+        if rscale is not None:
+            acc = acc * rscale[:S, None].to(at)
+        out[:S].zero_()
+        out[:S, :F] = acc.to(out.dtype)
+        return out, None
+    is_min = reduce == "min"
+    best = torch.zeros(S, F, dtype=X.dtype)
+    bi = torch.full((S, F), -1, dtype=torch.int64)
+    for k in range(int(cnt.max()) if S else 0):          # the k-th row of every segment that has one
+        r = torch.nonzero(cnt > k).flatten()
+        i = p[r] + k
+        c, b = X[i, :F], best[r]
+        if k == 0:
+            take = torch.ones_like(c, dtype=torch.bool)
+        else:
+            take = ((c < b) if is_min else (c > b)) | (torch.isnan(c) & ~torch.isnan(b))
+        best[r] = torch.where(take, c, b)
+        bi[r] = torch.where(take, i[:, None].expand_as(c), bi[r])
+    out[:S].zero_()
+    out[:S, :F] = best
+    if arg is not None:
+        if arg_in is not None and arg_in.shape[0]:
+            bi = torch.where(bi >= 0, torch.gather(arg_in[:, :F].long(), 0, bi.clamp_min(0)), bi)
+        arg[:S].fill_(-1)
+        arg[:S, :F] = bi.to(arg.dtype)
+    return out, arg
+
+
+def seg_bcast(seg_id, U, F, rscale=None, arg=None, out=None, out_dtype=None, ld_out=None):
+    """A segment's row broadcast to the segment's rows (gnn_readout.hip, seg_bcast_kernel):
+    ``out[i,f] = rscale[s] * U[s,f]`` with ``s = seg_id[i]`` (int32 ``[n]``), the product in
+    fp32 and rounded once (``rscale`` fp32 ``[S]``, default 1) -- the gradient of ``seg_reduce``'s
+    sum, and a forward op of its own (global conditioning ``x + u[batch]``).  With ``arg`` (int32
+    ``[S, ld]``, a max / min reduction's): ``out[i,f] = U[s,f]`` where ``arg[s,f] == i`` and 0
+    elsewhere, that reduction's gradient.  Padding columns are written 0.  The GPU compiles
+    the (U, out) pairs of ``wspmm``; ``out_dtype`` defaults to U's.  CPU tensors: PyTorch."""
+    if arg is not None and rscale is not None:
+        raise ValueError("seg_bcast: rscale or arg, not both")
+    n, S = seg_id.numel(), U.shape[0]
+    if out is None:
+        out = torch.empty(n, ld_out or U.shape[1], dtype=out_dtype or U.dtype, device=U.device)
+    if checks.enabled():
+        checks.index(seg_id, S, "seg_bcast seg_id")
+        checks.rows(out, n, "seg_bcast out")
+        checks.rows(rscale, S, "seg_bcast rscale")
+        if arg is not None:
+            _check_arg(arg, S, F, "seg_bcast")
+    if n and not S:
+        raise ValueError("seg_bcast: %d rows name segments of an empty U" % n)
+    if U.is_cuda:
+        _seg_gpu_operands("seg_bcast", (("seg_id", seg_id), ("arg", arg)), (("rscale", rscale),),
+                          (("U", U), ("out", out)))
+        native.hip().gnn_seg_bcast(seg_id.data_ptr(), U.data_ptr(), _ptr(rscale), _ptr(arg), out.data_ptr(), n, F,
+                                   U.shape[1], arg.shape[1] if arg is not None else 0, out.shape[1],
+                                   dtype_code(U.dtype), dtype_code(out.dtype), _st(U))
+        return out
+    at = _acc_dtype(U.dtype)
+    s = seg_id.long()
+    u = U[s, :F].to(at)
+    if arg is not None:
+        u = torch.where(arg[s, :F].long() == torch.arange(n)[:, None], u, torch.zeros((), dtype=at))
+    elif rscale is not None:
+        u = u * rscale[s].to(at)[:, None]
+    out[:n].zero_()
+    out[:n, :F] = u.to(out.dtype)
     return out
 
 
