@@ -175,6 +175,27 @@ int gnn_launch_seg_reduce(const int* ptr, const void* X, void* Y, const float* r
 int gnn_launch_seg_bcast(const int* seg_id, const void* U, const float* rscale, const int* arg, void* out, int n,
                          int F, int ldu, int ldarg, int ldo, int tin, int tout, hipStream_t st);
 
+// ---- gnn_geometry.hip: graphs from positions.  pos: fp32 [n, ldp], D coordinates per point;
+// gptr int32 [G + 1] / seg_id int32 [n]: the graphs of the batch.  radius_count writes deg [n],
+// radius_fill col (and d2, which may be null) at rowptr[i] .. rowptr[i + 1] in ascending
+// source id, for d2(i, j) <= r * r inside each graph (j != i unless loop).  pair_d2 writes
+// d2 [nnz] of any CSR's edges, pair_d2_bwd dpos [n, ldp] from g [nnz] = dL / d d2 over the CSR
+// and its transpose (eperm_t: transposed edge -> CSR edge).  lanes: the sub-group width, 0 =
+// from n / G (the search), nnz / n (pair_d2) or 2 nnz / n (its gradient).  Checks in this
+// order: -1 D outside 1..3 or a lanes value that is not compiled; -3 ldp < D, nnz < 0, or an r
+// that is negative or not finite; 0 without a launch for n <= 0 (and for nnz == 0 in the pair
+// kernels, whose caller then zeroes dpos); -3 a required pointer missing (every pointer but
+// radius_fill's d2) or G < 1; -4 the grid would overflow
+int gnn_launch_radius_count(const float* pos, const int* gptr, const int* seg_id, int* deg, int n, int G, int D,
+                            int ldp, float r, int loop, int lanes, hipStream_t st);
+int gnn_launch_radius_fill(const float* pos, const int* gptr, const int* seg_id, const int* rowptr, int* col,
+                           float* d2, int n, int G, int D, int ldp, float r, int loop, int lanes, hipStream_t st);
+int gnn_launch_pair_d2(const int* rowptr, const int* col, const float* pos, float* d2, int n, int nnz, int D, int ldp,
+                       int lanes, hipStream_t st);
+int gnn_launch_pair_d2_bwd(const int* rowptr, const int* col, const int* rowptr_t, const int* col_t,
+                           const int* eperm_t, const float* pos, const float* g, float* dpos, int n, int nnz, int D,
+                           int ldp, int lanes, hipStream_t st);
+
 // ---- gnn_edge_softmax.hip: softmax over each row's edges and its gradient.  s / p / dp / ds
 // are fp32, head-major [K, ld] (head k's edge e at k * ld + e); p may alias s and ds may
 // alias dp.  lanes: the sub-group width, 0 = from nnz / n_rows.  -3: a required pointer

@@ -264,6 +264,41 @@ PYBIND11_MODULE(_hip, m) {
         "gnn_seg_bcast");
   }, py::arg("seg_id"), py::arg("u"), py::arg("rscale"), py::arg("arg"), py::arg("out"), py::arg("n"), py::arg("F"),
      py::arg("ld_u"), py::arg("ld_arg"), py::arg("ld_out"), py::arg("u_type"), py::arg("out_type"), py::arg("st"));
+  // graphs from positions: radius search, pair distances and their gradient (gnn_geometry.hip)
+  m.def("gnn_radius_count", [](uint64_t pos, uint64_t gptr, uint64_t seg_id, uint64_t deg, int n, int n_graphs, int D,
+                               int ld_pos, float r, int loop, int lanes, uint64_t st) {
+    chk(gnn_launch_radius_count(Pt<const float>(pos), Pt<const int>(gptr), Pt<const int>(seg_id), Pt<int>(deg), n,
+                                n_graphs, D, ld_pos, r, loop, lanes, S(st)),
+        "gnn_radius_count");
+  }, py::arg("pos"), py::arg("gptr"), py::arg("seg_id"), py::arg("deg"), py::arg("n"), py::arg("n_graphs"),
+     py::arg("D"), py::arg("ld_pos"), py::arg("r"), py::arg("loop"), py::arg("lanes"), py::arg("st"));
+  m.def("gnn_radius_fill", [](uint64_t pos, uint64_t gptr, uint64_t seg_id, uint64_t rowptr, uint64_t col,
+                              uint64_t d2, int n, int n_graphs, int D, int ld_pos, float r, int loop, int lanes,
+                              uint64_t st) {
+    chk(gnn_launch_radius_fill(Pt<const float>(pos), Pt<const int>(gptr), Pt<const int>(seg_id),
+                               Pt<const int>(rowptr), Pt<int>(col), Pt<float>(d2), n, n_graphs, D, ld_pos, r, loop,
+                               lanes, S(st)),
+        "gnn_radius_fill");
+  }, py::arg("pos"), py::arg("gptr"), py::arg("seg_id"), py::arg("rowptr"), py::arg("col"), py::arg("d2"),
+     py::arg("n"), py::arg("n_graphs"), py::arg("D"), py::arg("ld_pos"), py::arg("r"), py::arg("loop"),
+     py::arg("lanes"), py::arg("st"));
+  m.def("gnn_pair_d2", [](uint64_t rowptr, uint64_t col, uint64_t pos, uint64_t d2, int n, int nnz, int D, int ld_pos,
+                          int lanes, uint64_t st) {
+    chk(gnn_launch_pair_d2(Pt<const int>(rowptr), Pt<const int>(col), Pt<const float>(pos), Pt<float>(d2), n, nnz, D,
+                           ld_pos, lanes, S(st)),
+        "gnn_pair_d2");
+  }, py::arg("rowptr"), py::arg("col"), py::arg("pos"), py::arg("d2"), py::arg("n"), py::arg("nnz"), py::arg("D"),
+     py::arg("ld_pos"), py::arg("lanes"), py::arg("st"));
+  m.def("gnn_pair_d2_bwd", [](uint64_t rowptr, uint64_t col, uint64_t rowptr_t, uint64_t col_t, uint64_t eperm_t,
+                              uint64_t pos, uint64_t g, uint64_t dpos, int n, int nnz, int D, int ld_pos, int lanes,
+                              uint64_t st) {
+    chk(gnn_launch_pair_d2_bwd(Pt<const int>(rowptr), Pt<const int>(col), Pt<const int>(rowptr_t),
+                               Pt<const int>(col_t), Pt<const int>(eperm_t), Pt<const float>(pos), Pt<const float>(g),
+                               Pt<float>(dpos), n, nnz, D, ld_pos, lanes, S(st)),
+        "gnn_pair_d2_bwd");
+  }, py::arg("rowptr"), py::arg("col"), py::arg("rowptr_t"), py::arg("col_t"), py::arg("eperm_t"), py::arg("pos"),
+     py::arg("g"), py::arg("dpos"), py::arg("n"), py::arg("nnz"), py::arg("D"), py::arg("ld_pos"), py::arg("lanes"),
+     py::arg("st"));
   // softmax over each row's edges and its gradient (gnn_edge_softmax.hip)
   m.def("gnn_edge_softmax_fwd", [](uint64_t rowptr, uint64_t s, uint64_t p, int n_rows, int nnz, int K, long ld,
                                    float scale, int lanes, uint64_t st) {

@@ -1,0 +1,350 @@
+// GNN track (beyond the reference): graphs from positions for MI355X -- the radius-graph
+// neighbour search over a batch of point sets, the squared pair distances of a CSR's edges
+// and their gradient with respect to the positions.
+//
+//   radius_count_kernel  deg[i]  = #{ j in graph(i) : d2(i, j) <= r2, j != i unless loop }
+//   radius_fill_kernel   col[rowptr[i] ..] = those j in ascending order, d2[..] their d2(i, j)
+//   pair_d2_kernel       d2[e]   = d2(i, col[e])  for the edges e of row i of any CSR
+//   pair_d2_bwd_kernel   dpos[i] = 2 ( sum_{e in in(i)}  g[e] (p_i - p_src(e))
+//                                    + sum_{e in out(i)} g[e] (p_i - p_dst(e)) )
+//
+// Positions are fp32 [n, ldp] with D coordinates per point, 1 <= D <= 3, ldp >= D; the columns
+// D <= c < ldp are never read.  graph(i) = [gptr[seg_id[i]], gptr[seg_id[i] + 1]) (gptr int32
+// [G + 1], seg_id int32 [n]: GraphBatch.gptr / .batch).
+//
+// The squared distance, one definition for every kernel of this file (sq_dist):
+//   dx = p_i[0] - p_j[0], dy = p_i[1] - p_j[1], dz = p_i[2] - p_j[2]     each one fp32 subtract
+//   d2 = fma(dz, dz, fma(dy, dy, dx * dx))                                explicit, no contraction
+// with the terms of absent coordinates dropped (D = 2: fma(dy, dy, dx * dx); D = 1: dx * dx).
+// i is the row (the destination), j the column (the source).
+//
+// Contract of the search.  r2 = r * r is one fp32 product, made on the host.  The boundary is
+// inclusive (d2 <= r2); a NaN d2 is not an edge (the compare is false); coincident points are
+// neighbours.  The search is brute force inside each graph, O(n_g^2): the algorithm for
+// molecules and other graphs of up to a few thousand points.  No cell lists, no periodic
+// boundaries, no cap on the neighbours of a point, no k-NN.
+//
+// Mapping (gnn_launch.h's blocks): wave64, 256-thread blocks, a sub-group of L lanes (8 / 16 /
+// 32 / 64) owns one destination i and loads p_i once.  Lane sl takes the candidates
+// j = g0 + sl, g0 + sl + L, ...: coalesced loads.  The predicate goes through a wave ballot cut
+// to the sub-group's L bits; a kept candidate's slot is base + popcount(bits below my lane),
+// and base advances by the popcount of the sub-group's bits.  That is the ascending order, and
+// the same code is both passes (FILL = false counts, FILL = true writes).  The loop condition
+// is itself a ballot, so that every lane of the wave runs every step and the ballots sit in
+// uniform control flow.  The CSR is therefore a function of the positions, gptr and seg_id
+// alone: the same for every L, grid and run.  No atomics.  A graph's rows, written with ids
+// relative to gptr[g], do not depend on where the graph stands in the batch.
+//
+// Bounds.  A seg_id outside [0, G) makes its row empty; graph ranges are cut to [0, n]; the
+// fill pass writes no slot at or past rowptr[i + 1], so a rowptr that does not come from the
+// count pass loses edges but writes nothing out of its rows.
+//
+// pair_d2_kernel: a sub-group owns row i, lane sl the edges e0 + sl, e0 + sl + L, ...  On a
+// radius graph it reproduces the fill pass's d2 bit for bit (the same sq_dist(p_i, p_j)).
+//
+// pair_d2_bwd_kernel: a sub-group owns node i.  In-edges come from the CSR row (rowptr, col),
+// out-edges from the transposed CSR (rowptr_t, col_t, eperm_t: transposed edge t is CSR edge
+// eperm_t[t], and col_t[t] is its destination).  Order of the sum, per coordinate, fp32:
+// lane sl starts from 0 and takes acc = fma(g[e], p_i - p_other, acc) over the in-edges
+// e0 + sl, e0 + sl + L, ... in that order, then over the out-edges t0 + sl, t0 + sl + L, ...
+// in that order; the L lane sums are combined by an xor butterfly (distances 1, 2, ... L / 2;
+// both partners of a step compute the same commutative sum); one product with 2 at the end.
+// The tree is a fixed function of the two degrees and L.  A self loop appears in both lists
+// and contributes 0 twice.  Columns D <= c < ldp of dpos are written 0; a node without edges
+// gets 0.  No atomics.
+#include "cgnn_common.h"
+#include "cgnn_api.h"
+#include "gnn_launch.h"
+#include <cmath>
+
+using namespace cgnn;
+using namespace cgnn::launch;
+
+namespace {
+
+template <int D>
+struct Point {
+  float c[D];
+};
+
+template <int D>
+__device__ __forceinline__ Point<D> load_point(const float* __restrict__ pos, int i, int ldp) {
+  Point<D> p;
+  const float* q = pos + (size_t)i * ldp;
+#pragma unroll
+  for (int c = 0; c < D; ++c) p.c[c] = q[c];
+  return p;
+}
+
+template <int D>
+__device__ __forceinline__ float sq_dist(const Point<D>& a, const Point<D>& b) {
+  const float dx = __fsub_rn(a.c[0], b.c[0]);
+  float d2 = __fmul_rn(dx, dx);
+  if (D > 1) {
+    const float dy = __fsub_rn(a.c[D > 1 ? 1 : 0], b.c[D > 1 ? 1 : 0]);
+    d2 = __fmaf_rn(dy, dy, d2);
+  }
+  if (D > 2) {
+    const float dz = __fsub_rn(a.c[D > 2 ? 2 : 0], b.c[D > 2 ? 2 : 0]);
+    d2 = __fmaf_rn(dz, dz, d2);
+  }
+  return d2;
+}
+
+// the row of this sub-group and its lane in it
+template <int L>
+__device__ __forceinline__ long sub_row(int& sub, int& sl) {
+  constexpr int RPW = 64 / L;
+  const int lane = threadIdx.x & 63;
+  sub = lane / L;
+  sl = lane - sub * L;
+  const unsigned blk = xcd_remap(blockIdx.x, gridDim.x);
+  return ((long)blk * (blockDim.x >> 6) + (threadIdx.x >> 6)) * RPW + sub;
+}
+
+template <int L>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int d = 1; d < L; d <<= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+
+}  // namespace
+
+// FILL = false: out = deg [n].  FILL = true: out = col, written at rowptr[i] ...; d2 may be null.
+template <int L, int D, bool FILL>
+__global__ __launch_bounds__(256) void radius_kernel(const float* __restrict__ pos, const int* __restrict__ gptr,
+                                                     const int* __restrict__ seg_id, const int* __restrict__ rowptr,
+                                                     int* __restrict__ out, float* __restrict__ d2out, int n, int G,
+                                                     int ldp, float r2, int loop) {
+  int sub, sl;
+  const long row = sub_row<L>(sub, sl);
+  const bool rv = row < n;
+  const int i = rv ? (int)row : 0;
+  int g0 = 0, g1 = 0;
+  if (rv) {
+    const int s = seg_id[i];
+    if (s >= 0 && s < G) {
+      g0 = max(gptr[s], 0);
+      g1 = min(gptr[s + 1], n);
+    }
+  }
+  Point<D> pi;
+#pragma unroll
+  for (int c = 0; c < D; ++c) pi.c[c] = 0.f;
+  if (g0 < g1) pi = load_point<D>(pos, i, ldp);
+  int base = 0, end = 0;
+  if (FILL && rv) {
+    base = rowptr[i];
+    end = rowptr[i + 1];
+  }
+  constexpr unsigned long long kGroup = L == 64 ? ~0ull : (1ull << (L & 63)) - 1ull;
+  const int shift = sub * L;
+  // the condition is wave-uniform: all 64 lanes run every step, finished sub-groups idle
+  for (int j0 = g0; __builtin_amdgcn_ballot_w64(j0 < g1) != 0ull; j0 += L) {
+    const int j = j0 + sl;
+    const bool ok = j < g1;
+    float d = 0.f;
+    bool keep = false;
+    if (ok) {
+      const Point<D> pj = load_point<D>(pos, j, ldp);
+      d = sq_dist<D>(pi, pj);
+      keep = d <= r2 && (loop || j != i);           // a NaN distance compares false
+    }
+    const unsigned long long m = (__builtin_amdgcn_ballot_w64(keep) >> shift) & kGroup;
+    if (FILL) {
+      const int slot = base + __popcll(m & ((1ull << sl) - 1ull));
+      if (keep && slot < end) {
+        out[slot] = j;
+        if (d2out) d2out[slot] = d;
+      }
+    }
+    base += __popcll(m);
+  }
+  if (!FILL && rv && sl == 0) out[i] = base;
+}
+
+template <int L, int D>
+__global__ __launch_bounds__(256) void pair_d2_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                      const float* __restrict__ pos, float* __restrict__ d2out,
+                                                      int n, int ldp) {
+  int sub, sl;
+  const long row = sub_row<L>(sub, sl);
+  if (row >= n) return;                             // no cross-lane traffic below
+  const int i = (int)row;
+  const int e0 = rowptr[i], e1 = rowptr[i + 1];
+  if (e0 >= e1) return;
+  const Point<D> pi = load_point<D>(pos, i, ldp);
+#pragma unroll 2
+  for (int e = e0 + sl; e < e1; e += L) d2out[e] = sq_dist<D>(pi, load_point<D>(pos, col[e], ldp));
+}
+
+template <int L, int D>
+__global__ __launch_bounds__(256) void pair_d2_bwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                          const int* __restrict__ rowptr_t,
+                                                          const int* __restrict__ col_t,
+                                                          const int* __restrict__ eperm_t,
+                                                          const float* __restrict__ pos, const float* __restrict__ g,
+                                                          float* __restrict__ dpos, int n, int ldp) {
+  int sub, sl;
+  const long row = sub_row<L>(sub, sl);
+  const bool rv = row < n;                          // the butterfly below needs every lane
+  const int i = rv ? (int)row : 0;
+  const int e0 = rv ? rowptr[i] : 0, e1 = rv ? rowptr[i + 1] : 0;
+  const int t0 = rv ? rowptr_t[i] : 0, t1 = rv ? rowptr_t[i + 1] : 0;
+  float acc[D];
+#pragma unroll
+  for (int c = 0; c < D; ++c) acc[c] = 0.f;
+  if (e0 < e1 || t0 < t1) {
+    const Point<D> pi = load_point<D>(pos, i, ldp);
+    for (int e = e0 + sl; e < e1; e += L) {
+      const Point<D> pj = load_point<D>(pos, col[e], ldp);
+      const float ge = g[e];
+#pragma unroll
+      for (int c = 0; c < D; ++c) acc[c] = __fmaf_rn(ge, __fsub_rn(pi.c[c], pj.c[c]), acc[c]);
+    }
+    for (int t = t0 + sl; t < t1; t += L) {
+      const Point<D> pj = load_point<D>(pos, col_t[t], ldp);
+      const float ge = g[eperm_t[t]];
+#pragma unroll
+      for (int c = 0; c < D; ++c) acc[c] = __fmaf_rn(ge, __fsub_rn(pi.c[c], pj.c[c]), acc[c]);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < D; ++c) acc[c] = group_sum<L>(acc[c]);
+  if (!rv) return;
+  for (int c = sl; c < ldp; c += L) {
+    float v = 0.f;
+#pragma unroll
+    for (int q = 0; q < D; ++q) v = c == q ? acc[q] : v;
+    dpos[(size_t)i * ldp + c] = __fmul_rn(2.f, v);
+  }
+}
+
+// ---------------------------------------------------------------- launchers
+
+namespace {
+
+// fn(Const<L>, Const<D>) for a compiled sub-group width and dimension; the caller has
+// checked both
+template <class Fn>
+int with_ld(int L, int D, Fn&& fn) {
+  auto dim = [&](auto l) {
+    if (D == 1) return fn(l, Const<1>{});
+    if (D == 2) return fn(l, Const<2>{});
+    return fn(l, Const<3>{});
+  };
+  if (L == 8) return dim(Const<8>{});
+  if (L == 16) return dim(Const<16>{});
+  if (L == 32) return dim(Const<32>{});
+  return dim(Const<64>{});
+}
+
+// the sub-group width for `per_row` candidates (or edges) per row on average: the average
+// row takes at most two steps of its sub-group
+int geo_auto_lanes(long per_row_total, int n_rows) {
+  if (per_row_total <= 16L * n_rows) return 8;
+  if (per_row_total <= 32L * n_rows) return 16;
+  if (per_row_total <= 64L * n_rows) return 32;
+  return 64;
+}
+
+bool geo_shape_ok(int D, int lanes) {
+  return D >= 1 && D <= 3 && (lanes == 0 || lanes == 8 || lanes == 16 || lanes == 32 || lanes == 64);
+}
+
+// blocks for n rows, or 0 when the launch would count its threads past 32 bits
+unsigned geo_grid(int L, int n) {
+  const long rpb = 4 * (64 / L);
+  const long b = ((long)n + rpb - 1) / rpb;
+  return b > (1L << 24) - 1 ? 0u : (unsigned)b;
+}
+
+// the checks the two passes of the search share, in the documented order; 1: go on
+int radius_prepare(int n, int G, int D, int ldp, float r, int lanes, int* L) {
+  if (!geo_shape_ok(D, lanes)) return -1;
+  if (ldp < D || !(r >= 0.f) || !std::isfinite(r)) return -3;
+  if (n <= 0) return 0;
+  // lanes = 0: from the average graph length (a caller that knows the longest graph passes
+  // its own choice: gnn/geometry.py)
+  *L = lanes ? lanes : geo_auto_lanes(n, G > 0 ? G : 1);
+  return 1;
+}
+
+}  // namespace
+
+// deg [n] of the radius graph of pos [n, ldp] over the graphs gptr [G + 1] / seg_id [n].
+// lanes: 0 = from n / G, or one of 8 / 16 / 32 / 64.  No allocation and no synchronisation:
+// capturable into a hipGraph.  Return codes: see cgnn_api.h.
+extern "C" int gnn_launch_radius_count(const float* pos, const int* gptr, const int* seg_id, int* deg, int n, int G,
+                                       int D, int ldp, float r, int loop, int lanes, hipStream_t st) {
+  int L = 0;
+  const int rc = radius_prepare(n, G, D, ldp, r, lanes, &L);
+  if (rc <= 0) return rc;
+  if (!pos || !gptr || !seg_id || !deg || G < 1) return -3;
+  const unsigned grid = geo_grid(L, n);
+  if (!grid) return -4;
+  const float r2 = r * r;
+  return with_ld(L, D, [&](auto l, auto d) {
+    hipLaunchKernelGGL((radius_kernel<decltype(l)::value, decltype(d)::value, false>), dim3(grid), dim3(256), 0, st,
+                       pos, gptr, seg_id, (const int*)nullptr, deg, (float*)nullptr, n, G, ldp, r2, loop);
+    return (int)hipGetLastError();
+  });
+}
+
+// col (and d2, which may be null) at rowptr[i] .. rowptr[i + 1], rowptr [n + 1] the exclusive
+// sum of the count pass's deg for the same arguments.  Capturable like the count.
+extern "C" int gnn_launch_radius_fill(const float* pos, const int* gptr, const int* seg_id, const int* rowptr,
+                                      int* col, float* d2, int n, int G, int D, int ldp, float r, int loop, int lanes,
+                                      hipStream_t st) {
+  int L = 0;
+  const int rc = radius_prepare(n, G, D, ldp, r, lanes, &L);
+  if (rc <= 0) return rc;
+  if (!pos || !gptr || !seg_id || !rowptr || !col || G < 1) return -3;
+  const unsigned grid = geo_grid(L, n);
+  if (!grid) return -4;
+  const float r2 = r * r;
+  return with_ld(L, D, [&](auto l, auto d) {
+    hipLaunchKernelGGL((radius_kernel<decltype(l)::value, decltype(d)::value, true>), dim3(grid), dim3(256), 0, st,
+                       pos, gptr, seg_id, rowptr, col, d2, n, G, ldp, r2, loop);
+    return (int)hipGetLastError();
+  });
+}
+
+// d2 [nnz] of the edges of the CSR (rowptr [n + 1], col) over pos [*, ldp].  lanes: 0 = from
+// nnz / n.  Capturable.
+extern "C" int gnn_launch_pair_d2(const int* rowptr, const int* col, const float* pos, float* d2, int n, int nnz,
+                                  int D, int ldp, int lanes, hipStream_t st) {
+  if (!geo_shape_ok(D, lanes)) return -1;
+  if (ldp < D || nnz < 0) return -3;
+  if (n <= 0 || nnz == 0) return 0;
+  if (!rowptr || !col || !pos || !d2) return -3;
+  const int L = lanes ? lanes : geo_auto_lanes(nnz, n);
+  const unsigned grid = geo_grid(L, n);
+  if (!grid) return -4;
+  return with_ld(L, D, [&](auto l, auto d) {
+    hipLaunchKernelGGL((pair_d2_kernel<decltype(l)::value, decltype(d)::value>), dim3(grid), dim3(256), 0, st, rowptr,
+                       col, pos, d2, n, ldp);
+    return (int)hipGetLastError();
+  });
+}
+
+// dpos [n, ldp] from g [nnz] = dL / d d2 over the CSR and its transpose (square: n rows, n
+// columns).  lanes: 0 = from 2 nnz / n.  With nnz == 0 nothing is launched and dpos is left to
+// the caller (ops.pair_d2_bwd zeroes it).  Capturable.
+extern "C" int gnn_launch_pair_d2_bwd(const int* rowptr, const int* col, const int* rowptr_t, const int* col_t,
+                                      const int* eperm_t, const float* pos, const float* g, float* dpos, int n,
+                                      int nnz, int D, int ldp, int lanes, hipStream_t st) {
+  if (!geo_shape_ok(D, lanes)) return -1;
+  if (ldp < D || nnz < 0) return -3;
+  if (n <= 0 || nnz == 0) return 0;
+  if (!rowptr || !col || !rowptr_t || !col_t || !eperm_t || !pos || !g || !dpos) return -3;
+  const int L = lanes ? lanes : geo_auto_lanes(2L * nnz, n);
+  const unsigned grid = geo_grid(L, n);
+  if (!grid) return -4;
+  return with_ld(L, D, [&](auto l, auto d) {
+    hipLaunchKernelGGL((pair_d2_bwd_kernel<decltype(l)::value, decltype(d)::value>), dim3(grid), dim3(256), 0, st,
+                       rowptr, col, rowptr_t, col_t, eperm_t, pos, g, dpos, n, ldp);
+    return (int)hipGetLastError();
+  });
+}

@@ -5,7 +5,7 @@ models run in CI); on a GPU the HIP kernels of csrc/kernels/gnn_sparse.hip (and
 gnn_wspmm.hip for the edge-weighted ops, gnn_pool.hip for max / min pooling,
 gnn_edge_softmax.hip for the softmax over a node's edges, gnn_espmm.hip for the aggregate
 with a feature row per edge, gnn_readout.hip for the reduction of each graph's node rows
-and its reverse) are mandatory -- a missing extension raises instead of silently falling back.
+and its reverse, gnn_geometry.hip for the radius-graph search and the pair distances) are mandatory -- a missing extension raises instead of silently falling back.
 """
 from __future__ import annotations
 
@@ -738,6 +738,246 @@ def edge_softmax_bwd(rowptr, p, dp, scale=1.0, out=None, lanes=None, nnz=None):
     pv, g = pv.to(at), dp.reshape(K, ld)[:, :rows.numel()].to(at)
     dot = torch.zeros(K, n, dtype=at).index_add_(1, rows, pv * g)
     out.view(K, ld)[:, :rows.numel()] = (scale * pv * (g - dot[:, rows])).to(out.dtype)
+    return out
+
+
+def _geo_args(what, pos, D, lanes):
+    """Shared validation of the geometry ops: (n, ldp, lanes)."""
+    if pos.dim() != 2:
+        raise ValueError("%s: pos must be [n, ldp], got shape %s" % (what, tuple(pos.shape)))
+    D = int(D)
+    if not 1 <= D <= 3:
+        raise ValueError("%s: D must be 1, 2 or 3, got %d" % (what, D))
+    if pos.shape[1] < D:
+        raise ValueError("%s: pos has %d columns for D = %d" % (what, pos.shape[1], D))
+    lanes = 0 if lanes is None else int(lanes)
+    if lanes not in (0,) + _ES_LANES:
+        raise ValueError("%s: lanes must be one of %s, got %d" % (what, _ES_LANES, lanes))
+    if pos.is_cuda:
+        _seg_gpu_operands(what, (), (("pos", pos),), ())
+    elif not pos.is_floating_point():
+        raise TypeError("%s: pos must be a floating-point tensor, got %s" % (what, pos.dtype))
+    return pos.shape[0], pos.shape[1], lanes
+
+
+def _radius_args(what, pos, D, r, gptr, seg_id, lanes):
+    n, ldp, lanes = _geo_args(what, pos, D, lanes)
+    r = float(r)
+    if not (r >= 0 and r < float("inf")):
+        raise ValueError("%s: r must be finite and not negative, got %r" % (what, r))
+    if gptr.dim() != 1 or gptr.numel() < 2 and n:
+        raise ValueError("%s: gptr must be a vector [G + 1] with G >= 1" % what)
+    if seg_id.dim() != 1 or seg_id.numel() != n:
+        raise ValueError("%s: seg_id must be [%d], got %s" % (what, n, tuple(seg_id.shape)))
+    if checks.enabled():
+        _check_ptr(gptr, n, what)
+        if int(gptr[-1]) != n:
+            raise ValueError("CGNN_CHECK: %s: gptr ends at %d but pos has %d rows" % (what, int(gptr[-1]), n))
+        checks.index(seg_id, gptr.numel() - 1, what + " seg_id")
+    return n, ldp, lanes, r
+
+
+def _sq_dist(a, b):
+    """``d2`` of the rows of ``a`` and ``b`` (``[..., D]``) by the kernels' definition: fp32
+    differences, then ``fma(dz, dz, fma(dy, dy, dx * dx))``.  PyTorch has no fma on the CPU: a
+    product of two fp32 values is exact in fp64, so each fma is one fp64 add rounded to fp32
+    (equal to the fused result except for rare double-rounding ties).  fp64 inputs: plain fp64."""
+    d = a - b
+    if d.dtype != torch.float32:
+        return (d * d).sum(-1)
+    d2 = d[..., 0] * d[..., 0]
+    for c in range(1, d.shape[-1]):
+        dc = d[..., c].double()
+        d2 = (dc * dc + d2.double()).float()
+    return d2
+
+
+def _radius_cpu(pos, D, r, gptr, loop):
+    """(deg, col, d2) of the radius graph on the CPU, graph by graph, ascending ids."""
+    n = pos.shape[0]
+    at = _acc_dtype(pos.dtype)
+    r2 = torch.tensor(r, dtype=at) * torch.tensor(r, dtype=at)
+    deg = torch.zeros(n, dtype=torch.int32)
+    cols, d2s = [], []
+    gp = gptr.tolist()
+    for g0, g1 in zip(gp[:-1], gp[1:]):
+        if g1 <= g0:
+            continue
+        p = pos[g0:g1, :D].to(at)
+        d2 = _sq_dist(p[:, None, :], p[None, :, :])          # [i (dst), j (src)]
+        keep = d2 <= r2                                       # False for NaN
+        if not loop:
+            keep &= ~torch.eye(g1 - g0, dtype=torch.bool)
+        deg[g0:g1] = keep.sum(1).to(torch.int32)
+        ij = keep.nonzero()                                   # sorted by (i, j)
+        cols.append((ij[:, 1] + g0).to(torch.int32))
+        d2s.append(d2[keep])
+    col = torch.cat(cols) if cols else torch.zeros(0, dtype=torch.int32)
+    d2 = torch.cat(d2s) if d2s else torch.zeros(0, dtype=at)
+    return deg, col, d2
+
+
+def radius_count(pos, D, r, gptr, seg_id, loop=False, lanes=None, out=None):
+    """The count pass of the radius-graph search (gnn_geometry.hip, radius_count_kernel):
+    ``deg[i]``, int32 ``[n]``, the number of sources ``j`` of node i's own graph
+    ``[gptr[g], gptr[g+1])``, ``g = seg_id[i]``, with ``d2(i, j) <= r * r`` and ``j != i`` unless
+    ``loop``.  ``pos`` is ``[n, ldp]`` with ``D`` (1..3) coordinates per point, fp32 on the GPU;
+    ``gptr`` int32 ``[G + 1]`` and ``seg_id`` int32 ``[n]`` are ``GraphBatch.gptr`` / ``.batch``.
+    ``d2 = fma(dz, dz, fma(dy, dy, dx * dx))`` of fp32 differences and ``r * r`` is one fp32
+    product; the boundary is inclusive, a NaN distance is no edge, coincident points are
+    neighbours.  Brute force inside each graph, O(n_g^2) -- for molecules and other graphs of
+    up to a few thousand points: no cell lists, no periodic boundaries, no neighbour cap, no
+    k-NN.  ``lanes``: force the sub-group width (8 / 16 / 32 / 64; default from ``n / G``); the
+    result is the same for every width.  ``out``: a preallocated ``deg``.  CPU tensors: PyTorch
+    with the same contract."""
+    n, ldp, lanes, r = _radius_args("radius_count", pos, D, r, gptr, seg_id, lanes)
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=pos.device)
+    if checks.enabled():
+        checks.rows(out, n, "radius_count out")
+    if pos.is_cuda:
+        _seg_gpu_operands("radius_count", (("gptr", gptr), ("seg_id", seg_id), ("out", out)), (), ())
+        native.hip().gnn_radius_count(pos.data_ptr(), gptr.data_ptr(), seg_id.data_ptr(), out.data_ptr(), n,
+                                      gptr.numel() - 1, int(D), ldp, r, int(bool(loop)), lanes, _st(pos))
+        return out
+    out[:n] = _radius_cpu(pos, int(D), r, gptr, loop)[0]
+    return out
+
+
+def radius_fill(pos, D, r, gptr, seg_id, rowptr, loop=False, lanes=None, out=None, d2=None, with_d2=False, nnz=None):
+    """The fill pass of the radius-graph search (gnn_geometry.hip, radius_fill_kernel):
+    ``col[rowptr[i] .. rowptr[i+1])`` = the neighbours of node i **in ascending source id**,
+    and with ``with_d2`` or a ``d2`` buffer their squared distances (fp32 ``[nnz]``) at the same
+    places.  ``rowptr`` (int32 ``[n + 1]``) is the exclusive sum of ``radius_count``'s ``deg`` for
+    the same arguments; nothing at or past ``rowptr[i+1]`` is written for row i.  Returns
+    ``(col, d2)``.  ``out`` / ``d2``: preallocated buffers of a known capacity; without ``out`` the
+    length is ``nnz``, or ``rowptr[-1]`` read back (one host sync).  No atomics: the CSR is a
+    function of ``pos`` and ``gptr`` alone -- not of ``lanes``, the grid or the run -- and a
+    graph's rows, with ids relative to ``gptr[g]``, do not depend on its place in the batch.
+    Contract, limits and the CPU branch as in ``radius_count``."""
+    n, ldp, lanes, r = _radius_args("radius_fill", pos, D, r, gptr, seg_id, lanes)
+    if rowptr.dim() != 1 or rowptr.numel() != n + 1:
+        raise ValueError("radius_fill: rowptr must be [%d], got %s" % (n + 1, tuple(rowptr.shape)))
+    if out is None:
+        nnz = int(rowptr[-1]) if nnz is None else int(nnz)
+        out = torch.empty(nnz, dtype=torch.int32, device=pos.device)
+    if d2 is None and with_d2:
+        d2 = torch.empty(out.numel(), dtype=_acc_dtype(pos.dtype), device=pos.device)
+    if checks.enabled():
+        _check_ptr(rowptr, 2 ** 31 - 1, "radius_fill")
+        for name, t in (("out", out), ("d2", d2)):
+            if t is not None and t.numel() < int(rowptr[-1]):
+                raise ValueError("CGNN_CHECK: radius_fill: %s holds %d edges, rowptr ends at %d"
+                                 % (name, t.numel(), int(rowptr[-1])))
+    if pos.is_cuda:
+        _seg_gpu_operands("radius_fill", (("gptr", gptr), ("seg_id", seg_id), ("rowptr", rowptr), ("out", out)),
+                          (("d2", d2),), ())
+        if out.numel() == 0:                                  # no edge to write (a null pointer)
+            return out, d2
+        native.hip().gnn_radius_fill(pos.data_ptr(), gptr.data_ptr(), seg_id.data_ptr(), rowptr.data_ptr(),
+                                     out.data_ptr(), _ptr(d2), n, gptr.numel() - 1, int(D), ldp, r, int(bool(loop)),
+                                     lanes, _st(pos))
+        return out, d2
+    deg, col, dd = _radius_cpu(pos, int(D), r, gptr, loop)
+    rp = rowptr.long()
+    # the kernel's rule for a rowptr that is not the count pass's: row i keeps its first
+    # rowptr[i+1] - rowptr[i] neighbours
+    cnt = deg.long()
+    start = torch.zeros(n + 1, dtype=torch.int64)
+    start[1:] = torch.cumsum(cnt, 0)
+    own = torch.repeat_interleave(torch.arange(n), cnt)
+    k = torch.arange(col.numel()) - start[own]
+    ok = k < (rp[1:] - rp[:-1])[own]
+    slot = rp[own] + k
+    out[slot[ok]] = col[ok].to(out.dtype)
+    if d2 is not None:
+        d2[slot[ok]] = dd[ok].to(d2.dtype)
+    return out, d2
+
+
+def _pair_args(what, rowptr, col, pos, D, lanes, nnz):
+    n, ldp, lanes = _geo_args(what, pos, D, lanes)
+    if rowptr.dim() != 1 or rowptr.numel() < 1 or rowptr.numel() - 1 > n:
+        raise ValueError("%s: rowptr describes %d rows for %d positions" % (what, rowptr.numel() - 1, n))
+    nnz = col.numel() if nnz is None else int(nnz)
+    if not 0 <= nnz <= col.numel():
+        raise ValueError("%s: nnz = %d with %d column ids" % (what, nnz, col.numel()))
+    checks.csr(rowptr, col, n, what)
+    if checks.enabled() and int(rowptr[-1]) > nnz:
+        raise ValueError("CGNN_CHECK: %s: rowptr ends at %d, nnz = %d" % (what, int(rowptr[-1]), nnz))
+    return rowptr.numel() - 1, ldp, lanes, nnz
+
+
+def pair_d2(rowptr, col, pos, D, out=None, lanes=None, nnz=None):
+    """The squared distance of each edge of a CSR (gnn_geometry.hip, pair_d2_kernel):
+    ``d2[e] = fma(dz, dz, fma(dy, dy, dx * dx))`` with ``dx = pos[i, 0] - pos[col[e], 0]`` ... in
+    fp32 for the edges e of row i (row = destination), fp32 ``[nnz]``.  ``pos`` is ``[n, ldp]``
+    with ``D`` (1..3) coordinates.  For graphs that do not come from the radius search (bond
+    graphs from ``GraphBatch.from_graphs``); on a radius graph it reproduces ``radius_fill``'s
+    ``d2`` bit for bit.  ``out``: a preallocated buffer of at least ``nnz`` (default
+    ``col.numel()``) elements; ``lanes`` as in ``edge_softmax``.  CPU tensors: PyTorch (fp64 for
+    fp64 positions)."""
+    n, ldp, lanes, nnz = _pair_args("pair_d2", rowptr, col, pos, D, lanes, nnz)
+    if out is None:
+        out = torch.empty(nnz, dtype=_acc_dtype(pos.dtype), device=pos.device)
+    if out.numel() < nnz:
+        raise ValueError("pair_d2: out holds %d edges, nnz = %d" % (out.numel(), nnz))
+    if pos.is_cuda:
+        _seg_gpu_operands("pair_d2", (("rowptr", rowptr), ("col", col)), (("out", out),), ())
+        native.hip().gnn_pair_d2(rowptr.data_ptr(), col.data_ptr(), pos.data_ptr(), out.data_ptr(), n, nnz, int(D),
+                                 ldp, lanes, _st(pos))
+        return out
+    rows = _row_ids(rowptr)
+    E = rows.numel()
+    at = _acc_dtype(pos.dtype)
+    out[:E] = _sq_dist(pos[rows, :D].to(at), pos[col[:E].long(), :D].to(at)).to(out.dtype)
+    return out
+
+
+def pair_d2_bwd(rowptr, col, rowptr_t, col_t, eperm_t, pos, g, D, out=None, lanes=None, nnz=None):
+    """The gradient of a scalar with respect to the positions through ``pair_d2``
+    (gnn_geometry.hip, pair_d2_bwd_kernel), given ``g[e] = dL / d d2[e]`` (fp32 ``[nnz]``):
+
+        dpos[i] = 2 (sum_{e in in(i)} g[e] (p_i - p_src(e)) + sum_{e in out(i)} g[e] (p_i - p_dst(e)))
+
+    The in-edges are row i of the CSR, the out-edges row i of the transposed CSR
+    (``rowptr_t``, ``col_t``, ``eperm_t`` as ``transposed_perm()`` returns them); the CSR is
+    square.  fp32 accumulation, in-edges in CSR order then out-edges in transposed order, in a
+    tree that is a fixed function of the two degrees and ``lanes``; the factor 2 once at the
+    end.  ``out`` is ``[n, ldp]`` like ``pos``: the columns ``D <= c < ldp`` are written 0 and a
+    node without edges gets 0.  No atomics: bit-identical from run to run.  CPU tensors:
+    PyTorch ``index_add_`` (fp64 for fp64 positions)."""
+    n, ldp, lanes, nnz = _pair_args("pair_d2_bwd", rowptr, col, pos, D, lanes, nnz)
+    if n != pos.shape[0] or rowptr_t.numel() != n + 1:
+        raise ValueError("pair_d2_bwd: a square CSR over the %d positions expected (%d rows, %d transposed rows)"
+                         % (pos.shape[0], n, rowptr_t.numel() - 1))
+    if g.dim() != 1 or g.numel() < nnz or col_t.numel() < nnz or eperm_t.numel() < nnz:
+        raise ValueError("pair_d2_bwd: g, col_t and eperm_t must hold %d edges" % nnz)
+    if out is None:
+        out = torch.empty_like(pos)
+    if out.shape != pos.shape:
+        raise ValueError("pair_d2_bwd: out must be %s like pos, got %s" % (tuple(pos.shape), tuple(out.shape)))
+    if checks.enabled():
+        checks.csr(rowptr_t, col_t, n, "pair_d2_bwd (transposed)")
+        checks.index(eperm_t[:nnz], max(nnz, 1), "pair_d2_bwd eperm_t")
+    if n == 0 or nnz == 0:
+        return out.zero_()
+    if pos.is_cuda:
+        _seg_gpu_operands("pair_d2_bwd", (("rowptr", rowptr), ("col", col), ("rowptr_t", rowptr_t), ("col_t", col_t),
+                                          ("eperm_t", eperm_t)), (("g", g), ("out", out)), ())
+        native.hip().gnn_pair_d2_bwd(rowptr.data_ptr(), col.data_ptr(), rowptr_t.data_ptr(), col_t.data_ptr(),
+                                     eperm_t.data_ptr(), pos.data_ptr(), g.data_ptr(), out.data_ptr(), n, nnz,
+                                     int(D), ldp, lanes, _st(pos))
+        return out
+    at = _acc_dtype(pos.dtype)
+    rows = _row_ids(rowptr)
+    E = rows.numel()
+    src = col[:E].long()
+    p = pos[:, :D].to(at)
+    w = g[:E].to(at)[:, None] * (p[rows] - p[src])
+    acc = torch.zeros(n, D, dtype=at).index_add_(0, rows, w).index_add_(0, src, -w)
+    out.zero_()
+    out[:, :D] = (2 * acc).to(out.dtype)
     return out
 
 

@@ -46,7 +46,7 @@ class GraphBatch:
     multi-edges kept, no self loops added; ``n = n_src`` nodes.  ``eperm`` (int64): the index
     in the concatenated input edge list of each CSR edge -- the sort is stable by (dst, input
     order) -- so edge rows go into CSR order as ``e_in[eperm]``.  ``gptr`` (int32 ``[G + 1]``),
-    ``batch`` (int32 ``[n]``, node -> graph), ``n_graphs``; ``count`` (int32 ``[G]``) and
+    ``batch`` (int32 ``[n]``, node -> graph), ``n_graphs``; ``count`` (int32 ``[G]``), ``max_count`` and
     ``inv_count`` (fp32: ``1 / count`` computed in fp64 and rounded once, 0 for an empty
     graph).  The chunk tables of the two-level reduction, for ``chunk = ops.READOUT_CHUNK``
     rows at construction: ``cptr`` (int32 ``[C + 1]``, the row boundaries of the chunks),
@@ -71,7 +71,8 @@ class GraphBatch:
         owner = torch.repeat_interleave(torch.arange(G), nch)
         start = gp[:-1][owner] + (torch.arange(C) - gchunk[:-1][owner]) * R
         self.chunk, self.n, self.n_src, self.n_graphs, self.n_chunks = R, n, n, G, C
-        self.single_pass = bool(C == 0 or int(cnt.max()) <= R)
+        self.max_count = int(cnt.max()) if G else 0
+        self.single_pass = bool(C == 0 or self.max_count <= R)
         self.gptr = _i32(gp, "the node count")
         self.batch = torch.repeat_interleave(torch.arange(G, dtype=torch.int32), cnt)
         self.count = cnt.to(torch.int32)
