@@ -195,6 +195,22 @@ int gnn_launch_pair_d2(const int* rowptr, const int* col, const float* pos, floa
 int gnn_launch_pair_d2_bwd(const int* rowptr, const int* col, const int* rowptr_t, const int* col_t,
                            const int* eperm_t, const float* pos, const float* g, float* dpos, int n, int nnz, int D,
                            int ldp, int lanes, hipStream_t st);
+// The k nearest candidates of each point (the neighbour cap of the radius search): a
+// candidate of row i is a j of its graph with j != i unless loop, a finite d2(i, j) and
+// d2(i, j) <= r * r (r = +inf: no radius); the row keeps the min(k, #candidates) smallest
+// keys (d2, j).  knn_select writes deg [n] and the largest kept key tau_d2 / tau_j [n]
+// ((-1, -1) for an empty row); knn_fill writes col (and d2, which may be null) at rowptr[i] ..
+// rowptr[i + 1] in ascending source id from those thresholds.  Checks in this order: -1 D
+// outside 1..3, k outside 1..64, a lanes value that is not compiled, or 0 < lanes < k (a
+// sub-group holds one key per lane); -3 ldp < D, or an r that is negative or NaN; 0 without a
+// launch for n <= 0; -3 a required pointer missing (every pointer but knn_fill's d2) or
+// G < 1; -4 the grid would overflow.  lanes = 0: the smallest compiled width that is >= k and
+// at least the radius search's choice (select), the radius search's choice (fill)
+int gnn_launch_knn_select(const float* pos, const int* gptr, const int* seg_id, int* deg, float* tau_d2, int* tau_j,
+                          int n, int G, int D, int ldp, int k, float r, int loop, int lanes, hipStream_t st);
+int gnn_launch_knn_fill(const float* pos, const int* gptr, const int* seg_id, const int* rowptr, const float* tau_d2,
+                        const int* tau_j, int* col, float* d2, int n, int G, int D, int ldp, int loop, int lanes,
+                        hipStream_t st);
 
 // ---- gnn_edge_softmax.hip: softmax over each row's edges and its gradient.  s / p / dp / ds
 // are fp32, head-major [K, ld] (head k's edge e at k * ld + e); p may alias s and ds may

@@ -264,7 +264,7 @@ PYBIND11_MODULE(_hip, m) {
         "gnn_seg_bcast");
   }, py::arg("seg_id"), py::arg("u"), py::arg("rscale"), py::arg("arg"), py::arg("out"), py::arg("n"), py::arg("F"),
      py::arg("ld_u"), py::arg("ld_arg"), py::arg("ld_out"), py::arg("u_type"), py::arg("out_type"), py::arg("st"));
-  // graphs from positions: radius search, pair distances and their gradient (gnn_geometry.hip)
+  // graphs from positions: radius and k-NN search, pair distances and their gradient (gnn_geometry.hip)
   m.def("gnn_radius_count", [](uint64_t pos, uint64_t gptr, uint64_t seg_id, uint64_t deg, int n, int n_graphs, int D,
                                int ld_pos, float r, int loop, int lanes, uint64_t st) {
     chk(gnn_launch_radius_count(Pt<const float>(pos), Pt<const int>(gptr), Pt<const int>(seg_id), Pt<int>(deg), n,
@@ -299,6 +299,25 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("rowptr"), py::arg("col"), py::arg("rowptr_t"), py::arg("col_t"), py::arg("eperm_t"), py::arg("pos"),
      py::arg("g"), py::arg("dpos"), py::arg("n"), py::arg("nnz"), py::arg("D"), py::arg("ld_pos"), py::arg("lanes"),
      py::arg("st"));
+  m.def("gnn_knn_select", [](uint64_t pos, uint64_t gptr, uint64_t seg_id, uint64_t deg, uint64_t tau_d2,
+                             uint64_t tau_j, int n, int n_graphs, int D, int ld_pos, int k, float r, int loop,
+                             int lanes, uint64_t st) {
+    chk(gnn_launch_knn_select(Pt<const float>(pos), Pt<const int>(gptr), Pt<const int>(seg_id), Pt<int>(deg),
+                              Pt<float>(tau_d2), Pt<int>(tau_j), n, n_graphs, D, ld_pos, k, r, loop, lanes, S(st)),
+        "gnn_knn_select");
+  }, py::arg("pos"), py::arg("gptr"), py::arg("seg_id"), py::arg("deg"), py::arg("tau_d2"), py::arg("tau_j"),
+     py::arg("n"), py::arg("n_graphs"), py::arg("D"), py::arg("ld_pos"), py::arg("k"), py::arg("r"), py::arg("loop"),
+     py::arg("lanes"), py::arg("st"));
+  m.def("gnn_knn_fill", [](uint64_t pos, uint64_t gptr, uint64_t seg_id, uint64_t rowptr, uint64_t tau_d2,
+                           uint64_t tau_j, uint64_t col, uint64_t d2, int n, int n_graphs, int D, int ld_pos,
+                           int loop, int lanes, uint64_t st) {
+    chk(gnn_launch_knn_fill(Pt<const float>(pos), Pt<const int>(gptr), Pt<const int>(seg_id), Pt<const int>(rowptr),
+                            Pt<const float>(tau_d2), Pt<const int>(tau_j), Pt<int>(col), Pt<float>(d2), n, n_graphs,
+                            D, ld_pos, loop, lanes, S(st)),
+        "gnn_knn_fill");
+  }, py::arg("pos"), py::arg("gptr"), py::arg("seg_id"), py::arg("rowptr"), py::arg("tau_d2"), py::arg("tau_j"),
+     py::arg("col"), py::arg("d2"), py::arg("n"), py::arg("n_graphs"), py::arg("D"), py::arg("ld_pos"),
+     py::arg("loop"), py::arg("lanes"), py::arg("st"));
   // softmax over each row's edges and its gradient (gnn_edge_softmax.hip)
   m.def("gnn_edge_softmax_fwd", [](uint64_t rowptr, uint64_t s, uint64_t p, int n_rows, int nnz, int K, long ld,
                                    float scale, int lanes, uint64_t st) {

@@ -1,9 +1,11 @@
 // GNN track (beyond the reference): graphs from positions for MI355X -- the radius-graph
-// neighbour search over a batch of point sets, the squared pair distances of a CSR's edges
-// and their gradient with respect to the positions.
+// and k-nearest-neighbour searches over a batch of point sets, the squared pair distances of a
+// CSR's edges and their gradient with respect to the positions.
 //
 //   radius_count_kernel  deg[i]  = #{ j in graph(i) : d2(i, j) <= r2, j != i unless loop }
 //   radius_fill_kernel   col[rowptr[i] ..] = those j in ascending order, d2[..] their d2(i, j)
+//   knn_select_kernel    deg[i]  = min(k, #candidates of i), (tau_d2, tau_j)[i] = the k-th key
+//   knn_fill_kernel      col[rowptr[i] ..] = the candidates with key <= tau, ascending j, and d2
 //   pair_d2_kernel       d2[e]   = d2(i, col[e])  for the edges e of row i of any CSR
 //   pair_d2_bwd_kernel   dpos[i] = 2 ( sum_{e in in(i)}  g[e] (p_i - p_src(e))
 //                                    + sum_{e in out(i)} g[e] (p_i - p_dst(e)) )
@@ -22,7 +24,17 @@
 // inclusive (d2 <= r2); a NaN d2 is not an edge (the compare is false); coincident points are
 // neighbours.  The search is brute force inside each graph, O(n_g^2): the algorithm for
 // molecules and other graphs of up to a few thousand points.  No cell lists, no periodic
-// boundaries, no cap on the neighbours of a point, no k-NN.
+// boundaries, no k-NN in feature space (D > 3).
+//
+// Contract of the k-NN search (the neighbour cap of the radius search is the same thing).  The
+// candidates of row i are the j of its graph with j != i unless loop, a finite d2(i, j) (not
+// NaN, not inf) and d2(i, j) <= r2; r = +inf means no radius (r2 = +inf: only the finiteness
+// test is left).  Row i keeps the min(k, #candidates) candidates with the smallest key
+// (d2, j), lexicographic, d2 compared as fp32: equal distances go to the lower id.  Keys are
+// distinct, so the kept set is a function of pos, gptr and seg_id alone.  The kept neighbours
+// are stored in ascending source id, like the radius fill, not in distance order: a row of
+// knn(k, r) is a subset of the row of radius(r) and bit-equal to it when that has at most k
+// entries.  1 <= k <= 64.  The result is in general a directed graph.
 //
 // Mapping (gnn_launch.h's blocks): wave64, 256-thread blocks, a sub-group of L lanes (8 / 16 /
 // 32 / 64) owns one destination i and loads p_i once.  Lane sl takes the candidates
@@ -34,6 +46,24 @@
 // uniform control flow.  The CSR is therefore a function of the positions, gptr and seg_id
 // alone: the same for every L, grid and run.  No atomics.  A graph's rows, written with ids
 // relative to gptr[g], do not depend on where the graph stands in the batch.
+//
+// knn_select_kernel: the same stream of candidates.  The sub-group holds its best keys
+// sorted, one per lane (k <= L; empty slots are (+inf, INT_MAX), which every candidate beats).
+// After the distance step the lanes whose candidate beats the row's current worst (the key of
+// lane k - 1) are pending; they are inserted one at a time, lowest lane first: the key is
+// broadcast, its rank is the popcount of the ballot "held key < new key" cut to the
+// sub-group, the lanes above the rank take their lower neighbour's key and the lane at the
+// rank the new one.  Before each insertion the pending lanes are tested against the new
+// worst, so after the first k candidates few remain: the distance pass plus about
+// k ln(n_g / k) insertions per row.  Both loops run while a ballot over the whole wave says
+// that some sub-group has work, so every ballot and shuffle sits in wave-uniform control
+// flow.  Row i gets deg[i], and its threshold, the largest kept key: tau_d2[i] / tau_j[i], or
+// (-1, -1) for a row that keeps nothing (no d2 is <= -1).  No LDS, no atomics.
+//
+// knn_fill_kernel: the loop of the radius fill with the predicate "key <= tau" (a NaN
+// distance compares false, +inf is above every tau, a d2 beyond r2 is above it too) and the
+// same ballot / popcount slots: ascending ids, nothing at or past rowptr[i + 1].  It takes no
+// k and no r, and any sub-group width whatever width selected.
 //
 // Bounds.  A seg_id outside [0, G) makes its row empty; graph ranges are cut to [0, n]; the
 // fill pass writes no slot at or past rowptr[i + 1], so a rowptr that does not come from the
@@ -55,6 +85,8 @@
 #include "cgnn_common.h"
 #include "cgnn_api.h"
 #include "gnn_launch.h"
+#include <algorithm>
+#include <climits>
 #include <cmath>
 
 using namespace cgnn;
@@ -162,6 +194,137 @@ __global__ __launch_bounds__(256) void radius_kernel(const float* __restrict__ p
     base += __popcll(m);
   }
   if (!FILL && rv && sl == 0) out[i] = base;
+}
+
+// (d, j) < (e, l), lexicographic; false when a distance is NaN
+__device__ __forceinline__ bool key_less(float d, int j, float e, int l) { return d < e || (d == e && j < l); }
+
+// deg [n], tau_d2 [n], tau_j [n]: see the header.  1 <= k <= L.
+template <int L, int D>
+__global__ __launch_bounds__(256) void knn_select_kernel(const float* __restrict__ pos, const int* __restrict__ gptr,
+                                                         const int* __restrict__ seg_id, int* __restrict__ deg,
+                                                         float* __restrict__ tau_d2, int* __restrict__ tau_j, int n,
+                                                         int G, int ldp, int k, float r2, int loop) {
+  int sub, sl;
+  const long row = sub_row<L>(sub, sl);
+  const bool rv = row < n;
+  const int i = rv ? (int)row : 0;
+  int g0 = 0, g1 = 0;
+  if (rv) {
+    const int s = seg_id[i];
+    if (s >= 0 && s < G) {
+      g0 = max(gptr[s], 0);
+      g1 = min(gptr[s + 1], n);
+    }
+  }
+  Point<D> pi;
+#pragma unroll
+  for (int c = 0; c < D; ++c) pi.c[c] = 0.f;
+  if (g0 < g1) pi = load_point<D>(pos, i, ldp);
+  constexpr unsigned long long kGroup = L == 64 ? ~0ull : (1ull << (L & 63)) - 1ull;
+  const int shift = sub * L;
+  const int worst = shift + k - 1;                  // the lane of the sub-group's k-th key
+  float hd = INFINITY;                              // held key of sorted position sl
+  int hj = INT_MAX;
+  int cnt = 0;                                      // candidates seen
+  // both conditions are wave-uniform: all 64 lanes run every step, finished sub-groups idle
+  for (int j0 = g0; __builtin_amdgcn_ballot_w64(j0 < g1) != 0ull; j0 += L) {
+    const int j = j0 + sl;
+    float d = 0.f;
+    bool pend = false;
+    if (j < g1) {
+      const Point<D> pj = load_point<D>(pos, j, ldp);
+      d = sq_dist<D>(pi, pj);
+      pend = d < INFINITY && d <= r2 && (loop || j != i);     // a NaN distance compares false
+    }
+    cnt += __popcll((__builtin_amdgcn_ballot_w64(pend) >> shift) & kGroup);
+    for (;;) {
+      const float wd = __shfl(hd, worst, 64);       // outside the &&: every lane takes part
+      const int wj = __shfl(hj, worst, 64);
+      pend = pend && key_less(d, j, wd, wj);
+      const unsigned long long all = __builtin_amdgcn_ballot_w64(pend);
+      if (all == 0ull) break;
+      const unsigned long long m = (all >> shift) & kGroup;
+      const int src = m ? __builtin_ctzll(m) : 0;   // the sub-group's lowest pending lane
+      const float nd = __shfl(d, shift + src, 64);
+      const int nj = __shfl(j, shift + src, 64);
+      const int rank = __popcll((__builtin_amdgcn_ballot_w64(key_less(hd, hj, nd, nj)) >> shift) & kGroup);
+      const float ud = __shfl_up(hd, 1, 64);
+      const int uj = __shfl_up(hj, 1, 64);
+      if (m) {                                      // rank <= k - 1 < L: the new key beat the worst
+        if (sl > rank) {
+          hd = ud;
+          hj = uj;
+        } else if (sl == rank) {
+          hd = nd;
+          hj = nj;
+        }
+        if (sl == src) pend = false;
+      }
+    }
+  }
+  const int kept = min(cnt, k);
+  const int last = shift + max(kept - 1, 0);
+  const float td = __shfl(hd, last, 64);
+  const int tj = __shfl(hj, last, 64);
+  if (rv && sl == 0) {
+    deg[i] = kept;
+    tau_d2[i] = kept ? td : -1.f;
+    tau_j[i] = kept ? tj : -1;
+  }
+}
+
+// col (and d2, which may be null) of the rows selected by knn_select_kernel
+template <int L, int D>
+__global__ __launch_bounds__(256) void knn_fill_kernel(const float* __restrict__ pos, const int* __restrict__ gptr,
+                                                       const int* __restrict__ seg_id, const int* __restrict__ rowptr,
+                                                       const float* __restrict__ tau_d2, const int* __restrict__ tau_j,
+                                                       int* __restrict__ out, float* __restrict__ d2out, int n, int G,
+                                                       int ldp, int loop) {
+  int sub, sl;
+  const long row = sub_row<L>(sub, sl);
+  const bool rv = row < n;
+  const int i = rv ? (int)row : 0;
+  int g0 = 0, g1 = 0;
+  if (rv) {
+    const int s = seg_id[i];
+    if (s >= 0 && s < G) {
+      g0 = max(gptr[s], 0);
+      g1 = min(gptr[s + 1], n);
+    }
+  }
+  Point<D> pi;
+#pragma unroll
+  for (int c = 0; c < D; ++c) pi.c[c] = 0.f;
+  if (g0 < g1) pi = load_point<D>(pos, i, ldp);
+  int base = 0, end = 0, tj = -1;
+  float td = -1.f;
+  if (rv) {
+    base = rowptr[i];
+    end = rowptr[i + 1];
+    td = tau_d2[i];
+    tj = tau_j[i];
+  }
+  constexpr unsigned long long kGroup = L == 64 ? ~0ull : (1ull << (L & 63)) - 1ull;
+  const int shift = sub * L;
+  // the condition is wave-uniform: all 64 lanes run every step, finished sub-groups idle
+  for (int j0 = g0; __builtin_amdgcn_ballot_w64(j0 < g1) != 0ull; j0 += L) {
+    const int j = j0 + sl;
+    float d = 0.f;
+    bool keep = false;
+    if (j < g1) {
+      const Point<D> pj = load_point<D>(pos, j, ldp);
+      d = sq_dist<D>(pi, pj);
+      keep = (d < td || (d == td && j <= tj)) && (loop || j != i);   // a NaN distance compares false
+    }
+    const unsigned long long m = (__builtin_amdgcn_ballot_w64(keep) >> shift) & kGroup;
+    const int slot = base + __popcll(m & ((1ull << sl) - 1ull));
+    if (keep && slot < end) {
+      out[slot] = j;
+      if (d2out) d2out[slot] = d;
+    }
+    base += __popcll(m);
+  }
 }
 
 template <int L, int D>
@@ -307,6 +470,56 @@ extern "C" int gnn_launch_radius_fill(const float* pos, const int* gptr, const i
   return with_ld(L, D, [&](auto l, auto d) {
     hipLaunchKernelGGL((radius_kernel<decltype(l)::value, decltype(d)::value, true>), dim3(grid), dim3(256), 0, st,
                        pos, gptr, seg_id, rowptr, col, d2, n, G, ldp, r2, loop);
+    return (int)hipGetLastError();
+  });
+}
+
+namespace {
+
+// the smallest compiled sub-group width that holds k keys, one per lane
+int knn_min_lanes(int k) { return k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : 64; }
+
+}  // namespace
+
+// deg / tau_d2 / tau_j [n] of the k nearest candidates of every point (see the header): pos
+// [n, ldp] over the graphs gptr [G + 1] / seg_id [n], 1 <= k <= 64, r >= 0 or +inf for no
+// radius.  lanes: 0 = the smallest compiled width that is >= k and at least the radius
+// search's choice, or one of 8 / 16 / 32 / 64 that is >= k.  No allocation and no
+// synchronisation: capturable into a hipGraph.  Return codes: see cgnn_api.h.
+extern "C" int gnn_launch_knn_select(const float* pos, const int* gptr, const int* seg_id, int* deg, float* tau_d2,
+                                     int* tau_j, int n, int G, int D, int ldp, int k, float r, int loop, int lanes,
+                                     hipStream_t st) {
+  if (!geo_shape_ok(D, lanes) || k < 1 || k > 64 || (lanes && lanes < k)) return -1;
+  if (ldp < D || !(r >= 0.f)) return -3;
+  if (n <= 0) return 0;
+  if (!pos || !gptr || !seg_id || !deg || !tau_d2 || !tau_j || G < 1) return -3;
+  const int L = lanes ? lanes : std::max(knn_min_lanes(k), geo_auto_lanes(n, G));
+  const unsigned grid = geo_grid(L, n);
+  if (!grid) return -4;
+  const float r2 = r * r;
+  return with_ld(L, D, [&](auto l, auto d) {
+    hipLaunchKernelGGL((knn_select_kernel<decltype(l)::value, decltype(d)::value>), dim3(grid), dim3(256), 0, st, pos,
+                       gptr, seg_id, deg, tau_d2, tau_j, n, G, ldp, k, r2, loop);
+    return (int)hipGetLastError();
+  });
+}
+
+// col (and d2, which may be null) at rowptr[i] .. rowptr[i + 1] for the thresholds of
+// gnn_launch_knn_select, rowptr [n + 1] the exclusive sum of its deg.  lanes: 0 = from n / G,
+// or any compiled width, whatever k and lanes selected.  Capturable like the select.
+extern "C" int gnn_launch_knn_fill(const float* pos, const int* gptr, const int* seg_id, const int* rowptr,
+                                   const float* tau_d2, const int* tau_j, int* col, float* d2, int n, int G, int D,
+                                   int ldp, int loop, int lanes, hipStream_t st) {
+  if (!geo_shape_ok(D, lanes)) return -1;
+  if (ldp < D) return -3;
+  if (n <= 0) return 0;
+  if (!pos || !gptr || !seg_id || !rowptr || !tau_d2 || !tau_j || !col || G < 1) return -3;
+  const int L = lanes ? lanes : geo_auto_lanes(n, G);
+  const unsigned grid = geo_grid(L, n);
+  if (!grid) return -4;
+  return with_ld(L, D, [&](auto l, auto d) {
+    hipLaunchKernelGGL((knn_fill_kernel<decltype(l)::value, decltype(d)::value>), dim3(grid), dim3(256), 0, st, pos,
+                       gptr, seg_id, rowptr, tau_d2, tau_j, col, d2, n, G, ldp, loop);
     return (int)hipGetLastError();
   });
 }

@@ -5,7 +5,7 @@ models run in CI); on a GPU the HIP kernels of csrc/kernels/gnn_sparse.hip (and
 gnn_wspmm.hip for the edge-weighted ops, gnn_pool.hip for max / min pooling,
 gnn_edge_softmax.hip for the softmax over a node's edges, gnn_espmm.hip for the aggregate
 with a feature row per edge, gnn_readout.hip for the reduction of each graph's node rows
-and its reverse, gnn_geometry.hip for the radius-graph search and the pair distances) are mandatory -- a missing extension raises instead of silently falling back.
+and its reverse, gnn_geometry.hip for the radius-graph and k-NN searches and the pair distances) are mandatory -- a missing extension raises instead of silently falling back.
 """
 from __future__ import annotations
 
@@ -765,6 +765,12 @@ def _radius_args(what, pos, D, r, gptr, seg_id, lanes):
     r = float(r)
     if not (r >= 0 and r < float("inf")):
         raise ValueError("%s: r must be finite and not negative, got %r" % (what, r))
+    _batch_args(what, n, gptr, seg_id)
+    return n, ldp, lanes, r
+
+
+def _batch_args(what, n, gptr, seg_id):
+    """The graphs of a batch of ``n`` points: ``gptr`` ``[G + 1]`` and ``seg_id`` ``[n]``."""
     if gptr.dim() != 1 or gptr.numel() < 2 and n:
         raise ValueError("%s: gptr must be a vector [G + 1] with G >= 1" % what)
     if seg_id.dim() != 1 or seg_id.numel() != n:
@@ -774,7 +780,6 @@ def _radius_args(what, pos, D, r, gptr, seg_id, lanes):
         if int(gptr[-1]) != n:
             raise ValueError("CGNN_CHECK: %s: gptr ends at %d but pos has %d rows" % (what, int(gptr[-1]), n))
         checks.index(seg_id, gptr.numel() - 1, what + " seg_id")
-    return n, ldp, lanes, r
 
 
 def _sq_dist(a, b):
@@ -826,8 +831,8 @@ def radius_count(pos, D, r, gptr, seg_id, loop=False, lanes=None, out=None):
     ``d2 = fma(dz, dz, fma(dy, dy, dx * dx))`` of fp32 differences and ``r * r`` is one fp32
     product; the boundary is inclusive, a NaN distance is no edge, coincident points are
     neighbours.  Brute force inside each graph, O(n_g^2) -- for molecules and other graphs of
-    up to a few thousand points: no cell lists, no periodic boundaries, no neighbour cap, no
-    k-NN.  ``lanes``: force the sub-group width (8 / 16 / 32 / 64; default from ``n / G``); the
+    up to a few thousand points: no cell lists, no periodic boundaries (``knn_select`` /
+    ``knn_fill`` cap a row at its k nearest).  ``lanes``: force the sub-group width (8 / 16 / 32 / 64; default from ``n / G``); the
     result is the same for every width.  ``out``: a preallocated ``deg``.  CPU tensors: PyTorch
     with the same contract."""
     n, ldp, lanes, r = _radius_args("radius_count", pos, D, r, gptr, seg_id, lanes)
@@ -879,9 +884,16 @@ def radius_fill(pos, D, r, gptr, seg_id, rowptr, loop=False, lanes=None, out=Non
                                      lanes, _st(pos))
         return out, d2
     deg, col, dd = _radius_cpu(pos, int(D), r, gptr, loop)
+    _fill_rows(deg, col, dd, rowptr, out, d2)
+    return out, d2
+
+
+def _fill_rows(deg, col, dd, rowptr, out, d2):
+    """The fill kernels' slots on the CPU: row i's ``deg[i]`` neighbours (``col`` / ``dd``, row
+    after row) go to ``rowptr[i] ..``.  The kernels' rule for a rowptr that is not the count
+    pass's: row i keeps its first ``rowptr[i+1] - rowptr[i]`` neighbours."""
+    n = deg.numel()
     rp = rowptr.long()
-    # the kernel's rule for a rowptr that is not the count pass's: row i keeps its first
-    # rowptr[i+1] - rowptr[i] neighbours
     cnt = deg.long()
     start = torch.zeros(n + 1, dtype=torch.int64)
     start[1:] = torch.cumsum(cnt, 0)
@@ -892,6 +904,148 @@ def radius_fill(pos, D, r, gptr, seg_id, rowptr, loop=False, lanes=None, out=Non
     out[slot[ok]] = col[ok].to(out.dtype)
     if d2 is not None:
         d2[slot[ok]] = dd[ok].to(d2.dtype)
+
+
+KNN_MAX = 64            # a sub-group holds one key per lane
+
+
+def _knn_min_lanes(k):
+    """The smallest compiled sub-group width that holds ``k`` keys."""
+    return next(L for L in _ES_LANES if L >= k)
+
+
+def _knn_cpu_d2(pos, D, g0, g1):
+    """``d2[i (dst), j (src)]`` of one graph and its "no self loop" mask."""
+    p = pos[g0:g1, :D].to(_acc_dtype(pos.dtype))
+    return _sq_dist(p[:, None, :], p[None, :, :]), ~torch.eye(g1 - g0, dtype=torch.bool)
+
+
+def knn_select(pos, D, k, gptr, seg_id, r=None, loop=False, lanes=None, deg=None, tau_d2=None, tau_j=None):
+    """The select pass of the k-NN search (gnn_geometry.hip, knn_select_kernel).  The
+    **candidates** of node i are the ``j`` of its own graph ``[gptr[g], gptr[g+1])``,
+    ``g = seg_id[i]``, with ``j != i`` unless ``loop``, a finite ``d2(i, j)`` (not NaN, not inf)
+    and ``d2(i, j) <= r * r`` (``r = None`` or ``inf``: no radius).  Row i keeps the
+    ``min(k, #candidates)`` candidates with the smallest key ``(d2, j)``, lexicographic with
+    ``d2`` compared as fp32: equal distances go to the lower id, so the kept set is a function
+    of ``pos`` and the graphs alone -- not of ``lanes``, the grid, the run or the graph's place
+    in the batch.  ``1 <= k <= 64``.  Returns ``(deg, tau_d2, tau_j)``: ``deg[i]`` int32 the
+    number kept, and the row's threshold, its largest kept key (``tau_d2`` fp32, ``tau_j``
+    int32; ``(-1, -1)`` for a row that keeps nothing), which ``knn_fill`` turns into the CSR.
+    ``pos``, ``D``, ``gptr``, ``seg_id`` and ``d2`` as in ``radius_count``.  ``lanes``: force
+    the sub-group width (8 / 16 / 32 / 64, at least ``k``: a sub-group holds one key per
+    lane; default the smallest such width that is at least ``radius_count``'s choice).
+    ``deg`` / ``tau_d2`` / ``tau_j``: preallocated outputs.  Brute force inside each graph,
+    O(n_g^2) distances plus about ``k ln(n_g / k)`` insertions per row.  CPU tensors: PyTorch
+    with the same contract (a stable sort of ``d2`` gives the tie rule; fp64 positions give
+    fp64 ``tau_d2``)."""
+    n, ldp, lanes = _geo_args("knn_select", pos, D, lanes)
+    k = int(k)
+    if not 1 <= k <= KNN_MAX:
+        raise ValueError("knn_select: k must be in 1..%d, got %d" % (KNN_MAX, k))
+    if lanes and lanes < k:
+        raise ValueError("knn_select: lanes = %d holds fewer than k = %d keys" % (lanes, k))
+    r = float("inf") if r is None else float(r)
+    if not r >= 0:
+        raise ValueError("knn_select: r must not be negative or NaN, got %r" % r)
+    _batch_args("knn_select", n, gptr, seg_id)
+    at = _acc_dtype(pos.dtype)
+    if deg is None:
+        deg = torch.empty(n, dtype=torch.int32, device=pos.device)
+    if tau_d2 is None:
+        tau_d2 = torch.empty(n, dtype=at, device=pos.device)
+    if tau_j is None:
+        tau_j = torch.empty(n, dtype=torch.int32, device=pos.device)
+    for name, t in (("deg", deg), ("tau_d2", tau_d2), ("tau_j", tau_j)):
+        if t.dim() != 1 or t.numel() < n:
+            raise ValueError("knn_select: %s must hold %d rows, got %s" % (name, n, tuple(t.shape)))
+    if pos.is_cuda:
+        _seg_gpu_operands("knn_select", (("gptr", gptr), ("seg_id", seg_id), ("deg", deg), ("tau_j", tau_j)),
+                          (("tau_d2", tau_d2),), ())
+        native.hip().gnn_knn_select(pos.data_ptr(), gptr.data_ptr(), seg_id.data_ptr(), deg.data_ptr(),
+                                    tau_d2.data_ptr(), tau_j.data_ptr(), n, gptr.numel() - 1, int(D), ldp, k, r,
+                                    int(bool(loop)), lanes, _st(pos))
+        return deg, tau_d2, tau_j
+    r2 = torch.tensor(r, dtype=at) * torch.tensor(r, dtype=at)
+    deg[:n] = 0
+    tau_d2[:n] = -1
+    tau_j[:n] = -1
+    gp = gptr.tolist()
+    for g0, g1 in zip(gp[:-1], gp[1:]):
+        if g1 <= g0:
+            continue
+        d2, off = _knn_cpu_d2(pos, int(D), g0, g1)
+        cand = torch.isfinite(d2) & (d2 <= r2)
+        if not loop:
+            cand &= off
+        cnt = cand.sum(1).clamp(max=k)
+        # stable: equal distances stay in ascending id; the non-candidates go last
+        key, order = torch.sort(torch.where(cand, d2, torch.full_like(d2, float("inf"))), dim=1, stable=True)
+        has = cnt > 0
+        last = (cnt - 1).clamp(min=0)[:, None]
+        deg[g0:g1] = cnt.to(deg.dtype)
+        tau_d2[g0:g1] = torch.where(has, key.gather(1, last)[:, 0], torch.full_like(key[:, 0], -1)).to(tau_d2.dtype)
+        tau_j[g0:g1] = torch.where(has, order.gather(1, last)[:, 0] + g0, torch.full_like(cnt, -1)).to(tau_j.dtype)
+    return deg, tau_d2, tau_j
+
+
+def knn_fill(pos, D, gptr, seg_id, rowptr, tau_d2, tau_j, loop=False, lanes=None, out=None, d2=None, with_d2=False,
+             nnz=None):
+    """The fill pass of the k-NN search (gnn_geometry.hip, knn_fill_kernel):
+    ``col[rowptr[i] .. rowptr[i+1])`` = the ``j`` of node i's graph whose key ``(d2(i, j), j)``
+    is at most the row's threshold ``(tau_d2[i], tau_j[i])`` from ``knn_select`` (``j != i``
+    unless ``loop``; a NaN or infinite distance is above every threshold), **in ascending
+    source id** -- not in distance order -- and with ``with_d2`` or a ``d2`` buffer their
+    squared distances at the same places.  ``rowptr`` (int32 ``[n + 1]``) is the exclusive sum
+    of ``knn_select``'s ``deg`` for the same arguments; nothing at or past ``rowptr[i+1]`` is
+    written for row i.  Takes no ``k`` and no ``r`` (the thresholds hold both), and ``lanes``
+    may be any compiled width whatever ``k`` was.  Returns ``(col, d2)``; ``out`` / ``d2`` /
+    ``nnz`` as in ``radius_fill``.  A row is a subset of the same row of ``radius_fill`` for
+    the same ``r``, and bit-equal to it when that has at most ``k`` entries."""
+    n, ldp, lanes = _geo_args("knn_fill", pos, D, lanes)
+    _batch_args("knn_fill", n, gptr, seg_id)
+    if rowptr.dim() != 1 or rowptr.numel() != n + 1:
+        raise ValueError("knn_fill: rowptr must be [%d], got %s" % (n + 1, tuple(rowptr.shape)))
+    for name, t in (("tau_d2", tau_d2), ("tau_j", tau_j)):
+        if t.dim() != 1 or t.numel() < n:
+            raise ValueError("knn_fill: %s must hold %d rows, got %s" % (name, n, tuple(t.shape)))
+    if out is None:
+        nnz = int(rowptr[-1]) if nnz is None else int(nnz)
+        out = torch.empty(nnz, dtype=torch.int32, device=pos.device)
+    if d2 is None and with_d2:
+        d2 = torch.empty(out.numel(), dtype=_acc_dtype(pos.dtype), device=pos.device)
+    if checks.enabled():
+        _check_ptr(rowptr, 2 ** 31 - 1, "knn_fill")
+        for name, t in (("out", out), ("d2", d2)):
+            if t is not None and t.numel() < int(rowptr[-1]):
+                raise ValueError("CGNN_CHECK: knn_fill: %s holds %d edges, rowptr ends at %d"
+                                 % (name, t.numel(), int(rowptr[-1])))
+    if pos.is_cuda:
+        _seg_gpu_operands("knn_fill", (("gptr", gptr), ("seg_id", seg_id), ("rowptr", rowptr), ("tau_j", tau_j),
+                                       ("out", out)), (("tau_d2", tau_d2), ("d2", d2)), ())
+        if out.numel() == 0:                                  # no edge to write (a null pointer)
+            return out, d2
+        native.hip().gnn_knn_fill(pos.data_ptr(), gptr.data_ptr(), seg_id.data_ptr(), rowptr.data_ptr(),
+                                  tau_d2.data_ptr(), tau_j.data_ptr(), out.data_ptr(), _ptr(d2), n,
+                                  gptr.numel() - 1, int(D), ldp, int(bool(loop)), lanes, _st(pos))
+        return out, d2
+    deg = torch.zeros(n, dtype=torch.int32)
+    cols, d2s = [], []
+    gp = gptr.tolist()
+    for g0, g1 in zip(gp[:-1], gp[1:]):
+        if g1 <= g0:
+            continue
+        dd, off = _knn_cpu_d2(pos, int(D), g0, g1)
+        td = tau_d2[g0:g1, None].to(dd.dtype)
+        ids = torch.arange(g0, g1)[None, :]
+        keep = (dd < td) | ((dd == td) & (ids <= tau_j[g0:g1, None]))       # False for NaN
+        if not loop:
+            keep &= off
+        deg[g0:g1] = keep.sum(1).to(torch.int32)
+        cols.append((keep.nonzero()[:, 1] + g0).to(torch.int32))              # sorted by (i, j)
+        d2s.append(dd[keep])
+    col = torch.cat(cols) if cols else torch.zeros(0, dtype=torch.int32)
+    dd = torch.cat(d2s) if d2s else torch.zeros(0, dtype=_acc_dtype(pos.dtype))
+    _fill_rows(deg, col, dd, rowptr, out, d2)
     return out, d2
 
 

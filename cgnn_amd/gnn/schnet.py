@@ -40,19 +40,22 @@ class SchNet(torch.nn.Module):
     """``E_g = sum_{i in g} MLP(x_i^T)`` with ``x^0 = embedding[z]`` and ``T = n_interactions``
     blocks ``x <- x + Dense(ssp(CFConv(x, e, c)))``, where ``e = GaussianSmearing(0, cutoff,
     n_gaussians)(d)`` and ``c = cosine_cutoff(d, cutoff)`` of the pair distances ``d`` of the
-    radius graph of ``cutoff``.  The output MLP is ``hidden -> hidden // 2 -> 1`` with a shifted
+    radius graph of ``cutoff`` (with ``max_num_neighbors``: of each atom's that many nearest
+    neighbours inside it, a directed neighbour list).  The output MLP is ``hidden -> hidden // 2 -> 1`` with a shifted
     softplus between.  ``z``: atomic numbers in ``[0, max_z)``.  The embedding rows are standard
     normal, the dense layers Glorot-uniform with zero biases, all drawn from ``generator``.
 
-    Out of scope: training on forces (a double backward through ``pair_distance``), periodic
-    cells, neighbour caps."""
+    Out of scope: training on forces (a double backward through ``pair_distance``) and
+    periodic cells."""
 
     def __init__(self, hidden: int = 128, n_filters: int = 128, n_interactions: int = 3, n_gaussians: int = 50,
-                 cutoff: float = 5.0, max_z: int = 100, generator: Optional[torch.Generator] = None):
+                 cutoff: float = 5.0, max_z: int = 100, generator: Optional[torch.Generator] = None,
+                 max_num_neighbors: Optional[int] = None):
         super().__init__()
         if hidden < 2 or n_interactions < 0 or not cutoff > 0:
             raise ValueError("SchNet: hidden >= 2, n_interactions >= 0 and cutoff > 0 expected")
         self.cutoff, self.max_z = float(cutoff), int(max_z)
+        self.max_num_neighbors = None if max_num_neighbors is None else int(max_num_neighbors)
         self.embedding = torch.nn.Parameter(torch.randn(self.max_z, hidden, generator=generator))
         self.smearing = GaussianSmearing(0.0, self.cutoff, n_gaussians)
         self.interactions = torch.nn.ModuleList(
@@ -61,8 +64,9 @@ class SchNet(torch.nn.Module):
         self.out2 = _Dense(hidden // 2, 1, generator=generator)
 
     def neighbors(self, pos: torch.Tensor, batch: Union[GraphBatch, torch.Tensor, None] = None) -> GraphBatch:
-        """The radius graph of the model's cutoff (one host sync: ``radius_graph``)."""
-        return radius_graph(pos, self.cutoff, batch)
+        """The radius graph of the model's cutoff, capped at the ``max_num_neighbors`` nearest
+        (one host sync: ``radius_graph``)."""
+        return radius_graph(pos, self.cutoff, batch, max_num_neighbors=self.max_num_neighbors)
 
     def forward(self, z: torch.Tensor, pos: torch.Tensor, batch: Union[GraphBatch, torch.Tensor, None] = None,
                 graph: Optional[GraphBatch] = None) -> torch.Tensor:
