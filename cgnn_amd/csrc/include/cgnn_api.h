@@ -211,6 +211,33 @@ int gnn_launch_knn_select(const float* pos, const int* gptr, const int* seg_id, 
 int gnn_launch_knn_fill(const float* pos, const int* gptr, const int* seg_id, const int* rowptr, const float* tau_d2,
                         const int* tau_j, int* col, float* d2, int n, int G, int D, int ldp, int loop, int lanes,
                         hipStream_t st);
+// Periodic cells (gnn_geometry.hip, "Periodic cells").  cell: fp32 [G, 9], the row-major 3 x 3
+// cell of each graph, row a = lattice vector a, only the leading D x D block read; nimg: int32
+// [G, 3], the image range of each axis, read clamped to 0 .. 7 (0: not periodic).  A candidate
+// of row i is (j, s): j of its graph, -nimg[a] <= s[a] <= nimg[a], kept when
+// d2(p_i, p_j + s . cell) <= r * r, (j, s) = (i, 0) left out unless loop.  radius_pbc_count
+// writes deg [n]; radius_pbc_fill col, shift (byte a = s[a] as int8, byte 3 = 0) and d2 (may
+// be null) at rowptr[i] .. rowptr[i + 1] in ascending (j, s), s lexicographic with the last
+// axis fastest.  pair_d2_pbc / pair_d2_pbc_bwd are pair_d2 / pair_d2_bwd for a CSR with such a
+// shift array; seg_id [n] names the cell of each row, and for pair_d2_pbc_bwd both ends of an
+// edge must have the same seg_id (a CSR that is block diagonal over the graphs).  The checks and their order are those
+// of the four launchers above, with cell, nimg, seg_id and the fill's shift among the
+// required pointers and G < 1 refused with them in the pair kernels too.  lanes = 0: from
+// n / G * max_images (the search; max_images, the largest number of images of a graph, is a
+// hint that only chooses the width), nnz / n (pair_d2_pbc) or 2 nnz / n (its gradient)
+int gnn_launch_radius_pbc_count(const float* pos, const int* gptr, const int* seg_id, const float* cell,
+                                const int* nimg, int* deg, int n, int G, int D, int ldp, float r, int loop, int lanes,
+                                int max_images, hipStream_t st);
+int gnn_launch_radius_pbc_fill(const float* pos, const int* gptr, const int* seg_id, const float* cell, const int* nimg,
+                               const int* rowptr, int* col, int* shift, float* d2, int n, int G, int D, int ldp,
+                               float r, int loop, int lanes, int max_images, hipStream_t st);
+int gnn_launch_pair_d2_pbc(const int* rowptr, const int* col, const int* shift, const float* pos, const float* cell,
+                           const int* seg_id, float* d2, int n, int nnz, int G, int D, int ldp, int lanes,
+                           hipStream_t st);
+int gnn_launch_pair_d2_pbc_bwd(const int* rowptr, const int* col, const int* shift, const int* rowptr_t,
+                               const int* col_t, const int* eperm_t, const float* pos, const float* cell,
+                               const int* seg_id, const float* g, float* dpos, int n, int nnz, int G, int D, int ldp,
+                               int lanes, hipStream_t st);
 
 // ---- gnn_edge_softmax.hip: softmax over each row's edges and its gradient.  s / p / dp / ds
 // are fp32, head-major [K, ld] (head k's edge e at k * ld + e); p may alias s and ds may

@@ -318,6 +318,50 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("pos"), py::arg("gptr"), py::arg("seg_id"), py::arg("rowptr"), py::arg("tau_d2"), py::arg("tau_j"),
      py::arg("col"), py::arg("d2"), py::arg("n"), py::arg("n_graphs"), py::arg("D"), py::arg("ld_pos"),
      py::arg("loop"), py::arg("lanes"), py::arg("st"));
+  // the same over periodic cells: image-shift radius search, shifted pair distances (gnn_geometry.hip)
+  m.def("gnn_radius_pbc_count", [](uint64_t pos, uint64_t gptr, uint64_t seg_id, uint64_t cell, uint64_t nimg,
+                                   uint64_t deg, int n, int n_graphs, int D, int ld_pos, float r, int loop, int lanes,
+                                   int max_images, uint64_t st) {
+    chk(gnn_launch_radius_pbc_count(Pt<const float>(pos), Pt<const int>(gptr), Pt<const int>(seg_id),
+                                    Pt<const float>(cell), Pt<const int>(nimg), Pt<int>(deg), n, n_graphs, D, ld_pos,
+                                    r, loop, lanes, max_images, S(st)),
+        "gnn_radius_pbc_count");
+  }, py::arg("pos"), py::arg("gptr"), py::arg("seg_id"), py::arg("cell"), py::arg("nimg"), py::arg("deg"),
+     py::arg("n"), py::arg("n_graphs"), py::arg("D"), py::arg("ld_pos"), py::arg("r"), py::arg("loop"),
+     py::arg("lanes"), py::arg("max_images"), py::arg("st"));
+  m.def("gnn_radius_pbc_fill", [](uint64_t pos, uint64_t gptr, uint64_t seg_id, uint64_t cell, uint64_t nimg,
+                                  uint64_t rowptr, uint64_t col, uint64_t shift, uint64_t d2, int n, int n_graphs,
+                                  int D, int ld_pos, float r, int loop, int lanes, int max_images, uint64_t st) {
+    chk(gnn_launch_radius_pbc_fill(Pt<const float>(pos), Pt<const int>(gptr), Pt<const int>(seg_id),
+                                   Pt<const float>(cell), Pt<const int>(nimg), Pt<const int>(rowptr), Pt<int>(col),
+                                   Pt<int>(shift), Pt<float>(d2), n, n_graphs, D, ld_pos, r, loop, lanes, max_images,
+                                   S(st)),
+        "gnn_radius_pbc_fill");
+  }, py::arg("pos"), py::arg("gptr"), py::arg("seg_id"), py::arg("cell"), py::arg("nimg"), py::arg("rowptr"),
+     py::arg("col"), py::arg("shift"), py::arg("d2"), py::arg("n"), py::arg("n_graphs"), py::arg("D"),
+     py::arg("ld_pos"), py::arg("r"), py::arg("loop"), py::arg("lanes"), py::arg("max_images"), py::arg("st"));
+  m.def("gnn_pair_d2_pbc", [](uint64_t rowptr, uint64_t col, uint64_t shift, uint64_t pos, uint64_t cell,
+                              uint64_t seg_id, uint64_t d2, int n, int nnz, int n_graphs, int D, int ld_pos, int lanes,
+                              uint64_t st) {
+    chk(gnn_launch_pair_d2_pbc(Pt<const int>(rowptr), Pt<const int>(col), Pt<const int>(shift), Pt<const float>(pos),
+                               Pt<const float>(cell), Pt<const int>(seg_id), Pt<float>(d2), n, nnz, n_graphs, D,
+                               ld_pos, lanes, S(st)),
+        "gnn_pair_d2_pbc");
+  }, py::arg("rowptr"), py::arg("col"), py::arg("shift"), py::arg("pos"), py::arg("cell"), py::arg("seg_id"),
+     py::arg("d2"), py::arg("n"), py::arg("nnz"), py::arg("n_graphs"), py::arg("D"), py::arg("ld_pos"),
+     py::arg("lanes"), py::arg("st"));
+  m.def("gnn_pair_d2_pbc_bwd", [](uint64_t rowptr, uint64_t col, uint64_t shift, uint64_t rowptr_t, uint64_t col_t,
+                                  uint64_t eperm_t, uint64_t pos, uint64_t cell, uint64_t seg_id, uint64_t g,
+                                  uint64_t dpos, int n, int nnz, int n_graphs, int D, int ld_pos, int lanes,
+                                  uint64_t st) {
+    chk(gnn_launch_pair_d2_pbc_bwd(Pt<const int>(rowptr), Pt<const int>(col), Pt<const int>(shift),
+                                   Pt<const int>(rowptr_t), Pt<const int>(col_t), Pt<const int>(eperm_t),
+                                   Pt<const float>(pos), Pt<const float>(cell), Pt<const int>(seg_id),
+                                   Pt<const float>(g), Pt<float>(dpos), n, nnz, n_graphs, D, ld_pos, lanes, S(st)),
+        "gnn_pair_d2_pbc_bwd");
+  }, py::arg("rowptr"), py::arg("col"), py::arg("shift"), py::arg("rowptr_t"), py::arg("col_t"), py::arg("eperm_t"),
+     py::arg("pos"), py::arg("cell"), py::arg("seg_id"), py::arg("g"), py::arg("dpos"), py::arg("n"), py::arg("nnz"),
+     py::arg("n_graphs"), py::arg("D"), py::arg("ld_pos"), py::arg("lanes"), py::arg("st"));
   // softmax over each row's edges and its gradient (gnn_edge_softmax.hip)
   m.def("gnn_edge_softmax_fwd", [](uint64_t rowptr, uint64_t s, uint64_t p, int n_rows, int nnz, int K, long ld,
                                    float scale, int lanes, uint64_t st) {

@@ -12,13 +12,20 @@ arguments of ``layers.CFConv``:
   ``ops.knn_fill``), optionally within a radius: the fixed fan-in entry of point-cloud models.
 * ``pair_distance`` -- the distance of each edge of a graph, differentiable with respect to
   the positions (``ops.pair_d2`` / ``ops.pair_d2_bwd``): exact, deterministic, no atomics.
+* periodic cells -- ``radius_graph(..., cell=, pbc=)`` searches the lattice images of every
+  source too (``ops.radius_pbc_count`` / ``ops.radius_pbc_fill``) and the graph carries the image
+  shift of each edge, which ``pair_distance`` adds to the source position
+  (``ops.pair_d2_pbc`` / ``ops.pair_d2_pbc_bwd``); ``image_ranges`` gives the image box of a
+  cutoff, ``wrap_positions`` brings positions into the cell.
 * ``GaussianSmearing`` / ``cosine_cutoff`` -- SchNet's radial basis and cutoff envelope, plain
   PyTorch: elementwise on ``[nnz, K]``.
 
 Limits.  The search is brute force inside each graph, O(n_g^2): right for molecules and other
-graphs of up to a few thousand points.  There are no cell lists for one large point cloud, no
-periodic boundaries and no k-NN in feature space (``D > 3``).  ``pair_distance`` is
-differentiable once: a double backward (training on forces) is not implemented.
+graphs of up to a few thousand points.  There are no cell lists for one large point cloud and
+no k-NN in feature space (``D > 3``).  Periodic cells: the radius search only (no k-NN and no
+neighbour cap over images), at most ``ops.PBC_NIMG_MAX`` images per direction, no gradient
+with respect to the cell (stress).  ``pair_distance`` is differentiable once: a double backward
+(training on forces) is not implemented.
 """
 from __future__ import annotations
 
@@ -80,13 +87,103 @@ def _graphs_of(what, p, batch):
     if base.n != n:
         raise ValueError("%s: the batch describes %d nodes, pos has %d rows" % (what, base.n, n))
     out = copy.copy(base)
+    out.shift = out.cell = None                                # a periodic graph's edges are not taken over
     out._move(p.device)
     return out
 
 
+def _cells_of(what, cell, pbc, G, D):
+    """``(cells, periodic)``: the cells as fp32 ``[G, D, D]`` on the CPU (one small read-back
+    for a cell on the device) and the periodic axes as bool ``[G, D]``."""
+    if not isinstance(cell, torch.Tensor) or not cell.is_floating_point():
+        raise TypeError("%s: cell must be a floating-point tensor" % what)
+    c = cell.detach().to("cpu", torch.float32)
+    if c.dim() == 2:
+        c = c[None].expand(G, -1, -1)
+    if c.dim() != 3 or c.shape[0] != G or c.shape[1] != c.shape[2] or c.shape[1] not in (D, 3):
+        raise ValueError("%s: cell must be [%d, %d], [3, 3] or [%d, ., .] for %d graphs, got %s"
+                         % (what, D, D, G, G, tuple(cell.shape)))
+    c = c[:, :D, :D].contiguous()
+    if not bool(torch.isfinite(c).all()):
+        raise ValueError("%s: the cell must be finite" % what)
+    pb = torch.as_tensor(pbc).to("cpu")
+    if pb.dtype != torch.bool:
+        raise TypeError("%s: pbc must be a bool, a bool per axis or bool [G, D]" % what)
+    if pb.dim() == 0:
+        pb = pb.expand(D)
+    if pb.dim() == 1 and pb.numel() in (D, 3):
+        pb = pb[None].expand(G, -1)
+    if pb.dim() != 2 or pb.shape[0] != G or pb.shape[1] not in (D, 3):
+        raise ValueError("%s: pbc must be a bool, %d (or 3) bools or [%d, %d], got shape %s"
+                         % (what, D, G, D, tuple(pb.shape)))
+    return c, pb[:, :D].contiguous()
+
+
+def image_ranges(cell: torch.Tensor, pbc, r: float) -> torch.Tensor:
+    """The lattice images a cutoff ``r`` reaches: int32 ``[G, 3]`` for cells ``[G, D, D]`` (or one
+    ``[D, D]`` cell: ``[1, 3]``), row a of a cell being lattice vector a.  ``pbc``: a bool, one per
+    axis, or ``[G, D]``.  Computed on the host in fp64: ``nimg[a] = ceil(r |b_a| (1 + 2^-20))`` for
+    a periodic axis, where ``b_a`` is column a of ``inv(cell)`` -- ``1 / |b_a|`` is the height of
+    the cell along a -- and 0 for any other axis (and for ``a >= D``).  With these ranges the
+    periodic ``radius_graph`` misses no pair of positions that lie in the cell
+    (``wrap_positions``): their fractional coordinates differ by less than 1, and a difference
+    vector of length at most ``r`` spans at most ``r |b_a|`` along axis a.  The fractional
+    coordinates are those of the whole cell, so an axis that is not periodic needs a lattice
+    vector too (a slab: its vacuum height).  Raises ``ValueError`` for a singular cell with a
+    periodic axis, and for a range above ``ops.PBC_NIMG_MAX``."""
+    r = float(r)
+    if not (r >= 0 and r < float("inf")):
+        raise ValueError("image_ranges: r must be finite and not negative, got %r" % r)
+    if not isinstance(cell, torch.Tensor) or cell.dim() not in (2, 3):
+        raise ValueError("image_ranges: cell must be [D, D] or [G, D, D]")
+    D = cell.shape[-1]
+    if not 1 <= D <= 3:
+        raise ValueError("image_ranges: cells of 1 to 3 dimensions expected, got %s" % (tuple(cell.shape),))
+    G = 1 if cell.dim() == 2 else cell.shape[0]
+    c, pb = _cells_of("image_ranges", cell, pbc, G, D)
+    nimg = torch.zeros(G, 3, dtype=torch.int32)
+    for g in range(G):
+        if not bool(pb[g].any()):
+            continue
+        C = c[g].double()
+        scale = float(C.abs().max())
+        if scale == 0 or abs(float(torch.linalg.det(C / scale))) < 1e-12:
+            raise ValueError("image_ranges: the cell of graph %d is singular and has a periodic axis" % g)
+        b = torch.linalg.inv(C).norm(dim=0)                    # |b_a|, the inverse heights
+        for a in range(D):
+            if not bool(pb[g, a]):
+                continue
+            k = math.ceil(r * float(b[a]) * (1.0 + 2.0 ** -20))
+            if k > ops.PBC_NIMG_MAX:
+                raise ValueError("image_ranges: the cutoff %g reaches %d images along axis %d of graph %d, whose "
+                                 "cell is %g high; at most %d are searched (use a supercell)"
+                                 % (r, k, a, g, 1.0 / float(b[a]), ops.PBC_NIMG_MAX))
+            nimg[g, a] = k
+    return nimg
+
+
+def wrap_positions(pos: torch.Tensor, cell: torch.Tensor, pbc=True,
+                   batch: Union[GraphBatch, torch.Tensor, None] = None) -> torch.Tensor:
+    """``pos`` moved by lattice vectors so that the fractional coordinates ``pos @ inv(cell)`` of
+    the periodic axes lie in ``[0, 1)`` (up to the rounding of ``pos``'s dtype): ``pos -
+    floor(frac) @ cell`` over the periodic axes.  ``cell``, ``pbc`` and ``batch`` as in
+    ``radius_graph``.  Plain PyTorch on ``pos``'s device, differentiable with respect to ``pos``
+    (the shift is piecewise constant)."""
+    _positions(pos, "wrap_positions")
+    n, D = pos.shape
+    b = _graphs_of("wrap_positions", pos, batch)
+    c, pb = _cells_of("wrap_positions", cell, pbc, b.n_graphs, D)
+    if n == 0:
+        return pos
+    C = c.to(pos.device, pos.dtype)[b.batch.long()]             # [n, D, D]
+    frac = torch.linalg.solve(C.transpose(1, 2), pos.detach()[:, :, None])[:, :, 0]       # frac @ C = pos
+    k = torch.floor(frac) * pb.to(pos.device, pos.dtype)[b.batch.long()]
+    return pos - (k[:, None, :] @ C)[:, 0, :]
+
+
 def radius_graph(pos: torch.Tensor, r: float, batch: Union[GraphBatch, torch.Tensor, None] = None,
                  loop: bool = False, lanes: Optional[int] = None,
-                 max_num_neighbors: Optional[int] = None) -> GraphBatch:
+                 max_num_neighbors: Optional[int] = None, cell: Optional[torch.Tensor] = None, pbc=True) -> GraphBatch:
     """The graph of all pairs of points of the same graph at most ``r`` apart.
 
     ``pos`` is ``[n, D]``, ``D`` in 1..3.  ``batch``: a ``GraphBatch`` (its ``gptr`` / ``batch``
@@ -109,8 +206,28 @@ def radius_graph(pos: torch.Tensor, r: float, batch: Union[GraphBatch, torch.Ten
     ``GraphBatch`` to avoid that).  Deterministic: no atomics, the same CSR for every ``lanes``
     (the sub-group width, default from the longest graph), grid and run.
 
-    Brute force inside each graph, O(n_g^2): for molecules and graphs of up to a few thousand
-    points.  No cell lists, no periodic boundaries."""
+    ``cell``: ``None``, or the periodic cell -- ``[D, D]`` (or ``[3, 3]``, of which the leading
+    ``D x D`` block is used) for all graphs, or one per graph ``[G, D, D]``; row a is lattice
+    vector a.  ``pbc``: which axes are periodic, a bool, one per axis, or ``[G, D]``.  A source
+    is then searched in the lattice images ``image_ranges(cell, pbc, r)`` of every periodic
+    axis too: row i holds the pairs (j, s) with ``|p_i - (p_j + s @ cell)|^2 <= r * r`` in
+    ascending (j, s), without (i, 0) unless ``loop`` -- (i, s != 0) is an edge, an atom sees its
+    own images, and two atoms may share several edges.  The result also carries ``.shift`` (int32
+    ``[nnz]``, the packed s of each edge: ``ops.radius_pbc_fill``), ``.cell`` (fp32 ``[G, 9]`` on the
+    device) and ``shifts()`` (int32 ``[nnz, 3]``); ``pair_distance`` and ``SchNet`` use them, every
+    other layer sees an ordinary CSR.  **The neighbour list is complete when the positions lie
+    in the cell** -- bring them there with ``wrap_positions`` -- and for positions outside it
+    misses the images beyond the ranges.  A cell on the device costs one small read-back (like
+    a ``gptr`` on the device), a CPU cell none.  ``max_num_neighbors`` together with ``cell``
+    raises ``NotImplementedError``; a cutoff that needs more than ``ops.PBC_NIMG_MAX`` images
+    along an axis raises (``image_ranges``).
+
+    Brute force inside each graph, O(n_g^2) (times the number of images): for molecules,
+    crystal cells and graphs of up to a few thousand points.  No cell lists."""
+    if cell is not None:
+        if max_num_neighbors is not None:
+            raise NotImplementedError("radius_graph: max_num_neighbors over periodic images is not implemented")
+        return _radius_graph_pbc(pos, r, batch, loop, lanes, cell, pbc)
     if max_num_neighbors is not None:
         return knn_graph(pos, max_num_neighbors, batch, loop, r=r, lanes=lanes)
     _positions(pos, "radius_graph")
@@ -127,6 +244,37 @@ def radius_graph(pos: torch.Tensor, r: float, batch: Union[GraphBatch, torch.Ten
     out.rowptr = rp.to(torch.int32)
     out.col, out.d2 = ops.radius_fill(p, D, r, out.gptr, out.batch, out.rowptr, loop=loop, lanes=L, nnz=nnz,
                                       with_d2=True)
+    out.eperm = torch.arange(nnz, dtype=torch.int64, device=p.device)
+    out._tperm = None
+    return out
+
+
+def _radius_graph_pbc(pos, r, batch, loop, lanes, cell, pbc):
+    _positions(pos, "radius_graph")
+    p = pos.detach().contiguous()
+    n, D = p.shape
+    out = _graphs_of("radius_graph", p, batch)
+    G = out.n_graphs
+    c, pb = _cells_of("radius_graph", cell, pbc, G, D)
+    nimg = image_ranges(c, pb, r) if G else torch.zeros(0, 3, dtype=torch.int32)
+    cell9 = torch.zeros(G, 3, 3)
+    cell9[:, :D, :D] = c
+    out.cell = cell9.view(G, 9).to(p.device)
+    images = (2 * nimg.long() + 1).prod(1)
+    M = int(images.max()) if G else 1
+    # the sub-group width as in the radius search, from a bound on the candidates of the longest
+    # row that needs no read-back: the longest graph (a host integer) times the most images
+    L = _auto_lanes(out.max_count * M) if lanes is None else lanes
+    nd = nimg.to(p.device)
+    deg = ops.radius_pbc_count(p, D, r, out.gptr, out.batch, out.cell, nd, loop=loop, lanes=L, max_images=M)
+    rp = torch.zeros(n + 1, dtype=torch.int64, device=p.device)
+    rp[1:] = torch.cumsum(deg, 0, dtype=torch.int64)
+    nnz = int(rp[-1])                                         # the one host sync
+    if nnz >= 2 ** 31:
+        raise ValueError("radius_graph: %d edges do not fit int32" % nnz)
+    out.rowptr = rp.to(torch.int32)
+    out.col, out.shift, out.d2 = ops.radius_pbc_fill(p, D, r, out.gptr, out.batch, out.cell, nd, out.rowptr,
+                                                     loop=loop, lanes=L, max_images=M, nnz=nnz, with_d2=True)
     out.eperm = torch.arange(nnz, dtype=torch.int64, device=p.device)
     out._tperm = None
     return out
@@ -177,7 +325,10 @@ class _PairDistance(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pos, g, squared):
         p = pos.detach().contiguous()
-        d2 = ops.pair_d2(g.rowptr, g.col, p, p.shape[1])
+        if getattr(g, "shift", None) is not None:
+            d2 = ops.pair_d2_pbc(g.rowptr, g.col, g.shift, p, p.shape[1], g.cell, g.batch)
+        else:
+            d2 = ops.pair_d2(g.rowptr, g.col, p, p.shape[1])
         out = d2 if squared else torch.sqrt(d2)
         ctx.g, ctx.squared = g, squared
         ctx.save_for_backward(p, out)
@@ -193,7 +344,12 @@ class _PairDistance(torch.autograd.Function):
         else:                                                # d sqrt(d2) = 1 / (2 d), 0 at d = 0
             w = torch.where(out == 0, torch.zeros_like(gd), gd / (2 * out))
         rp_t, col_t, eperm_t = g.transposed_perm()
-        dpos = ops.pair_d2_bwd(g.rowptr, g.col, rp_t, col_t, eperm_t, p, w.to(out.dtype).contiguous(), p.shape[1])
+        w = w.to(out.dtype).contiguous()
+        if getattr(g, "shift", None) is not None:
+            dpos = ops.pair_d2_pbc_bwd(g.rowptr, g.col, g.shift, rp_t, col_t, eperm_t, p, w, p.shape[1], g.cell,
+                                       g.batch)
+        else:
+            dpos = ops.pair_d2_bwd(g.rowptr, g.col, rp_t, col_t, eperm_t, p, w, p.shape[1])
         return dpos, None, None
 
 
@@ -206,8 +362,10 @@ def pair_distance(pos: torch.Tensor, g, squared: bool = False) -> torch.Tensor:
     forward is ``ops.pair_d2`` (and one square root), the backward ``ops.pair_d2_bwd`` over the
     graph and its transpose, built once per graph -- fp32, deterministic, no atomics.  The
     gradient of the distance is defined as 0 where the distance is 0 (coincident points, self
-    loops).  Differentiable **once**: a double backward, as training on forces needs, is not
-    implemented and raises."""
+    loops).  A periodic ``radius_graph`` (one with ``.shift`` and ``.cell``) gives
+    ``|p_i - (p_j + s @ cell)|`` through ``ops.pair_d2_pbc`` / ``ops.pair_d2_pbc_bwd``; the gradient
+    goes to the positions only, not to the cell.  Differentiable **once**: a double backward,
+    as training on forces needs, is not implemented and raises."""
     _positions(pos, "pair_distance")
     n = g.rowptr.numel() - 1
     if pos.shape[0] != n or getattr(g, "n_src", n) != n:

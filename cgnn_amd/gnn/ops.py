@@ -831,8 +831,9 @@ def radius_count(pos, D, r, gptr, seg_id, loop=False, lanes=None, out=None):
     ``d2 = fma(dz, dz, fma(dy, dy, dx * dx))`` of fp32 differences and ``r * r`` is one fp32
     product; the boundary is inclusive, a NaN distance is no edge, coincident points are
     neighbours.  Brute force inside each graph, O(n_g^2) -- for molecules and other graphs of
-    up to a few thousand points: no cell lists, no periodic boundaries (``knn_select`` /
-    ``knn_fill`` cap a row at its k nearest).  ``lanes``: force the sub-group width (8 / 16 / 32 / 64; default from ``n / G``); the
+    up to a few thousand points: no cell lists (``knn_select`` / ``knn_fill`` cap a row at its k
+    nearest; ``radius_pbc_count`` / ``radius_pbc_fill`` search the images of a periodic cell).
+    ``lanes``: force the sub-group width (8 / 16 / 32 / 64; default from ``n / G``); the
     result is the same for every width.  ``out``: a preallocated ``deg``.  CPU tensors: PyTorch
     with the same contract."""
     n, ldp, lanes, r = _radius_args("radius_count", pos, D, r, gptr, seg_id, lanes)
@@ -1129,6 +1130,273 @@ def pair_d2_bwd(rowptr, col, rowptr_t, col_t, eperm_t, pos, g, D, out=None, lane
     src = col[:E].long()
     p = pos[:, :D].to(at)
     w = g[:E].to(at)[:, None] * (p[rows] - p[src])
+    acc = torch.zeros(n, D, dtype=at).index_add_(0, rows, w).index_add_(0, src, -w)
+    out.zero_()
+    out[:, :D] = (2 * acc).to(out.dtype)
+    return out
+
+
+PBC_NIMG_MAX = 7        # the largest image range of an axis; the kernels clamp what they read to it
+
+
+def _pbc_args(what, G, cell, nimg, on_gpu):
+    """The cells ``[G, 9]`` and, for the search, the image ranges ``[G, 3]`` of ``G`` graphs."""
+    if cell.dim() != 2 or tuple(cell.shape) != (G, 9):
+        raise ValueError("%s: cell must be [%d, 9], got %s" % (what, G, tuple(cell.shape)))
+    if nimg is not None and tuple(nimg.shape) != (G, 3):
+        raise ValueError("%s: nimg must be [%d, 3], got %s" % (what, G, tuple(nimg.shape)))
+    if on_gpu:
+        _seg_gpu_operands(what, (("nimg", nimg),), (("cell", cell),), ())
+    elif not cell.is_floating_point() or (nimg is not None and nimg.is_floating_point()):
+        raise TypeError("%s: a floating-point cell and integer nimg expected" % what)
+    if checks.enabled() and nimg is not None and nimg.numel():
+        if int(nimg.min()) < 0 or int(nimg.max()) > PBC_NIMG_MAX:
+            raise ValueError("CGNN_CHECK: %s: nimg outside 0..%d" % (what, PBC_NIMG_MAX))
+
+
+def _pbc_images(ni):
+    """The image box of one graph, int64 ``[M, D]``: ``-ni[a] .. ni[a]`` per axis in
+    lexicographic order, the last axis fastest."""
+    return torch.cartesian_prod(*[torch.arange(-k, k + 1) for k in ni]).reshape(-1, len(ni))
+
+
+def _pbc_offset(S, C):
+    """``S . C`` by the kernels' definition, ``fma(s2, C[2], fma(s1, C[1], s0 * C[0]))``, for
+    shifts ``S`` ``[..., D]`` and cells ``C`` ``[..., D, D]`` (fp32: the fma emulated as in
+    ``_sq_dist``; fp64: plain fp64 in the same order)."""
+    at = C.dtype
+    off = S[..., 0:1].to(at) * C[..., 0, :]
+    for a in range(1, S.shape[-1]):
+        if at == torch.float32:
+            off = (S[..., a:a + 1].double() * C[..., a, :].double() + off.double()).float()
+        else:
+            off = S[..., a:a + 1].to(at) * C[..., a, :] + off
+    return off
+
+
+def _pack_shift(S):
+    """int32 ``[...]`` from shifts ``[..., D]``: byte a = ``S[..., a]`` as an int8, byte 3 = 0."""
+    w = torch.zeros(S.shape[:-1], dtype=torch.int64)
+    for a in range(S.shape[-1]):
+        w |= (S[..., a].long() & 0xFF) << (8 * a)
+    return w.to(torch.int32)
+
+
+def unpack_shift(shift, D=3):
+    """int32 ``[nnz, D]`` from the packed ``shift`` ``[nnz]`` of ``radius_pbc_fill``."""
+    b = torch.stack([(shift >> (8 * a)) & 0xFF for a in range(int(D))], -1)
+    return torch.where(b >= 128, b - 256, b).to(torch.int32)
+
+
+def _radius_pbc_cpu(pos, D, r, gptr, cell, nimg, loop):
+    """(deg, col, shift, d2) of the periodic radius graph on the CPU, graph by graph, in
+    ascending (j, image)."""
+    n = pos.shape[0]
+    at = _acc_dtype(pos.dtype)
+    r2 = torch.tensor(r, dtype=at) * torch.tensor(r, dtype=at)
+    deg = torch.zeros(n, dtype=torch.int32)
+    cols, shs, d2s = [], [], []
+    gp = gptr.tolist()
+    for g, (g0, g1) in enumerate(zip(gp[:-1], gp[1:])):
+        if g1 <= g0:
+            continue
+        p = pos[g0:g1, :D].to(at)
+        S = _pbc_images(nimg[g, :D].clamp(0, PBC_NIMG_MAX).tolist())
+        q = p[:, None, :] + _pbc_offset(S, cell[g].view(3, 3)[:D, :D].to(at))[None, :, :]    # [j, m, D]
+        d2 = _sq_dist(p[:, None, None, :], q[None, :, :, :])                                     # [i, j, m]
+        keep = d2 <= r2                                       # False for NaN
+        if not loop:
+            home = int((S == 0).all(1).nonzero()[0])
+            idx = torch.arange(g1 - g0)
+            keep[idx, idx, home] = False
+        deg[g0:g1] = keep.sum((1, 2)).to(torch.int32)
+        ijm = keep.nonzero()                                  # sorted by (i, j, m)
+        cols.append((ijm[:, 1] + g0).to(torch.int32))
+        shs.append(_pack_shift(S[ijm[:, 2]]))
+        d2s.append(d2[keep])
+    col = torch.cat(cols) if cols else torch.zeros(0, dtype=torch.int32)
+    shift = torch.cat(shs) if shs else torch.zeros(0, dtype=torch.int32)
+    d2 = torch.cat(d2s) if d2s else torch.zeros(0, dtype=at)
+    return deg, col, shift, d2
+
+
+def _max_images(max_images):
+    return 1 if max_images is None else max(1, min(int(max_images), (2 * PBC_NIMG_MAX + 1) ** 3))
+
+
+def radius_pbc_count(pos, D, r, gptr, seg_id, cell, nimg, loop=False, lanes=None, max_images=None, out=None):
+    """The count pass of the periodic radius search (gnn_geometry.hip, radius_pbc_kernel):
+    ``deg[i]``, int32 ``[n]``, the number of candidates ``(j, s)`` of node i that are kept.  ``j``
+    runs over node i's own graph ``g``, the image ``s`` over the box ``-nimg[g, a] <= s[a] <=
+    nimg[g, a]``, ``a < D``; kept when ``d2(p_i, p_j + s . C_g) <= r * r``, where ``(j, s) = (i,
+    0)`` is left out unless ``loop`` -- ``(i, s != 0)`` is an edge: an atom sees its own images.
+    ``cell`` is fp32 ``[G, 9]``, the row-major 3 x 3 cell of each graph (row a = lattice vector
+    a, only the leading ``D x D`` block is read); ``nimg`` int32 ``[G, 3]`` with values in
+    ``0..PBC_NIMG_MAX`` (0: the axis is not periodic; the kernels clamp to that range).  The
+    offset is ``off[c] = fma(s2, C[2][c], fma(s1, C[1][c], s0 * C[0][c]))`` in fp32 with the terms
+    of absent axes dropped, the image ``q = p_j + off`` one fp32 add and ``d2`` that of
+    ``radius_count`` between ``p_i`` and ``q``: with ``nimg`` all zero the result is
+    ``radius_count``'s bit for bit.  Inclusive boundary, a NaN distance is no edge.  For finite
+    inputs ``(i, j, s)`` is an edge iff ``(j, i, -s)`` is.  ``pos``, ``gptr``, ``seg_id``, ``lanes``
+    and ``out`` as in ``radius_count``; the default ``lanes`` comes from ``n / G * max_images``
+    (``max_images``: the largest number of images of a graph, a hint for that choice only).
+    Brute force, ``O(n_g^2 M_g)`` per graph.  CPU tensors: PyTorch with the same contract."""
+    n, ldp, lanes, r = _radius_args("radius_pbc_count", pos, D, r, gptr, seg_id, lanes)
+    _pbc_args("radius_pbc_count", gptr.numel() - 1, cell, nimg, pos.is_cuda)
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=pos.device)
+    if checks.enabled():
+        checks.rows(out, n, "radius_pbc_count out")
+    if pos.is_cuda:
+        _seg_gpu_operands("radius_pbc_count", (("gptr", gptr), ("seg_id", seg_id), ("out", out)), (), ())
+        native.hip().gnn_radius_pbc_count(pos.data_ptr(), gptr.data_ptr(), seg_id.data_ptr(), cell.data_ptr(),
+                                          nimg.data_ptr(), out.data_ptr(), n, gptr.numel() - 1, int(D), ldp, r,
+                                          int(bool(loop)), lanes, _max_images(max_images), _st(pos))
+        return out
+    out[:n] = _radius_pbc_cpu(pos, int(D), r, gptr, cell, nimg, loop)[0]
+    return out
+
+
+def radius_pbc_fill(pos, D, r, gptr, seg_id, cell, nimg, rowptr, loop=False, lanes=None, max_images=None, out=None,
+                    shift=None, d2=None, with_d2=False, nnz=None):
+    """The fill pass of the periodic radius search: ``col`` / ``shift`` (and ``d2``) at
+    ``rowptr[i] .. rowptr[i+1])`` = the kept candidates ``(j, s)`` of node i **in ascending (j,
+    m)**, ``m`` the index of ``s`` in lexicographic order with the last axis fastest.  ``shift``
+    is int32 ``[nnz]``: byte a holds ``s[a]`` as a two's-complement int8, byte 3 is 0, so 0 is
+    the home image (``unpack_shift``).  Returns ``(col, shift, d2)``.  ``rowptr``, ``out`` / ``shift``
+    / ``d2`` / ``nnz`` as in ``radius_fill``: nothing at or past ``rowptr[i+1]`` is written for
+    row i.  No atomics: the CSR is a function of ``pos``, the graphs, ``cell`` and ``nimg`` alone
+    -- not of ``lanes``, the grid or the run.  Contract as in ``radius_pbc_count``."""
+    n, ldp, lanes, r = _radius_args("radius_pbc_fill", pos, D, r, gptr, seg_id, lanes)
+    _pbc_args("radius_pbc_fill", gptr.numel() - 1, cell, nimg, pos.is_cuda)
+    if rowptr.dim() != 1 or rowptr.numel() != n + 1:
+        raise ValueError("radius_pbc_fill: rowptr must be [%d], got %s" % (n + 1, tuple(rowptr.shape)))
+    if out is None:
+        nnz = int(rowptr[-1]) if nnz is None else int(nnz)
+        out = torch.empty(nnz, dtype=torch.int32, device=pos.device)
+    if shift is None:
+        shift = torch.empty(out.numel(), dtype=torch.int32, device=pos.device)
+    if d2 is None and with_d2:
+        d2 = torch.empty(out.numel(), dtype=_acc_dtype(pos.dtype), device=pos.device)
+    if shift.numel() < out.numel():
+        raise ValueError("radius_pbc_fill: shift holds %d edges, out %d" % (shift.numel(), out.numel()))
+    if checks.enabled():
+        _check_ptr(rowptr, 2 ** 31 - 1, "radius_pbc_fill")
+        for name, t in (("out", out), ("shift", shift), ("d2", d2)):
+            if t is not None and t.numel() < int(rowptr[-1]):
+                raise ValueError("CGNN_CHECK: radius_pbc_fill: %s holds %d edges, rowptr ends at %d"
+                                 % (name, t.numel(), int(rowptr[-1])))
+    if pos.is_cuda:
+        _seg_gpu_operands("radius_pbc_fill", (("gptr", gptr), ("seg_id", seg_id), ("rowptr", rowptr), ("out", out),
+                                              ("shift", shift)), (("d2", d2),), ())
+        if out.numel() == 0:                                  # no edge to write (a null pointer)
+            return out, shift, d2
+        native.hip().gnn_radius_pbc_fill(pos.data_ptr(), gptr.data_ptr(), seg_id.data_ptr(), cell.data_ptr(),
+                                         nimg.data_ptr(), rowptr.data_ptr(), out.data_ptr(), shift.data_ptr(),
+                                         _ptr(d2), n, gptr.numel() - 1, int(D), ldp, r, int(bool(loop)), lanes,
+                                         _max_images(max_images), _st(pos))
+        return out, shift, d2
+    deg, col, sh, dd = _radius_pbc_cpu(pos, int(D), r, gptr, cell, nimg, loop)
+    _fill_rows(deg, col, dd, rowptr, out, d2)
+    _fill_rows(deg, sh, dd, rowptr, shift, None)
+    return out, shift, d2
+
+
+def _pair_pbc_args(what, n, shift, nnz, cell, seg_id, on_gpu):
+    if shift.dim() != 1 or shift.numel() < nnz:
+        raise ValueError("%s: shift must hold %d edges, got %s" % (what, nnz, tuple(shift.shape)))
+    if seg_id.dim() != 1 or seg_id.numel() < n:
+        raise ValueError("%s: seg_id must hold %d rows, got %s" % (what, n, tuple(seg_id.shape)))
+    if cell.dim() != 2 or cell.shape[1] != 9 or (cell.shape[0] < 1 and n):
+        raise ValueError("%s: cell must be [G, 9] with G >= 1, got %s" % (what, tuple(cell.shape)))
+    _pbc_args(what, cell.shape[0], cell, None, on_gpu)
+    if on_gpu:
+        _seg_gpu_operands(what, (("shift", shift), ("seg_id", seg_id)), (), ())
+    if checks.enabled():
+        checks.index(seg_id[:n], max(cell.shape[0], 1), what + " seg_id")
+
+
+def _edge_offsets(rows, shift, cell, seg_id, D, at):
+    """``shift[e] . cell(graph of row(e))`` ``[E, D]`` in ``at``, by the kernels' definition."""
+    C = cell.view(-1, 3, 3)[seg_id[rows].long()][:, :D, :D].to(at)
+    return _pbc_offset(unpack_shift(shift[:rows.numel()], D).long(), C)
+
+
+def pair_d2_pbc(rowptr, col, shift, pos, D, cell, seg_id, out=None, lanes=None, nnz=None):
+    """``pair_d2`` for a CSR with image shifts (gnn_geometry.hip, pair_d2_pbc_kernel):
+    ``d2[e] = d2(p_i, p_col[e] + s_e . C)`` for the edges e of row i, ``s_e`` unpacked from
+    ``shift[e]`` (``radius_pbc_fill``'s format; any int8 values) and ``C = cell[seg_id[i]]``
+    (``cell`` fp32 ``[G, 9]``, ``seg_id`` int32 ``[n]``; a ``seg_id`` outside ``[0, G)`` reads a zero
+    cell).  The offset and the sum are those of ``radius_pbc_count``: on a periodic radius graph
+    it reproduces ``radius_pbc_fill``'s ``d2`` bit for bit.  ``out`` / ``lanes`` / ``nnz`` as in
+    ``pair_d2``.  CPU tensors: PyTorch (fp64 for fp64 positions)."""
+    n, ldp, lanes, nnz = _pair_args("pair_d2_pbc", rowptr, col, pos, D, lanes, nnz)
+    _pair_pbc_args("pair_d2_pbc", n, shift, nnz, cell, seg_id, pos.is_cuda)
+    if out is None:
+        out = torch.empty(nnz, dtype=_acc_dtype(pos.dtype), device=pos.device)
+    if out.numel() < nnz:
+        raise ValueError("pair_d2_pbc: out holds %d edges, nnz = %d" % (out.numel(), nnz))
+    if pos.is_cuda:
+        _seg_gpu_operands("pair_d2_pbc", (("rowptr", rowptr), ("col", col)), (("out", out),), ())
+        native.hip().gnn_pair_d2_pbc(rowptr.data_ptr(), col.data_ptr(), shift.data_ptr(), pos.data_ptr(),
+                                     cell.data_ptr(), seg_id.data_ptr(), out.data_ptr(), n, nnz, cell.shape[0],
+                                     int(D), ldp, lanes, _st(pos))
+        return out
+    D = int(D)
+    rows = _row_ids(rowptr)
+    E = rows.numel()
+    at = _acc_dtype(pos.dtype)
+    q = pos[col[:E].long(), :D].to(at) + _edge_offsets(rows, shift, cell, seg_id, D, at)
+    out[:E] = _sq_dist(pos[rows, :D].to(at), q).to(out.dtype)
+    return out
+
+
+def pair_d2_pbc_bwd(rowptr, col, shift, rowptr_t, col_t, eperm_t, pos, g, D, cell, seg_id, out=None, lanes=None,
+                    nnz=None):
+    """``pair_d2_bwd`` through ``pair_d2_pbc`` (gnn_geometry.hip, pair_d2_pbc_bwd_kernel):
+
+        dpos[i] = 2 (sum_{e in in(i)} g[e] (p_i - (p_src(e) + off_e)) + sum_{e in out(i)} g[e] (p_i - (p_dst(e) - off_e)))
+
+    with ``off_e = s_e . C`` as in ``pair_d2_pbc``.  Operands, order of the sum, ``out`` and the
+    CPU branch as in ``pair_d2_bwd``; the gradient goes to the positions only (none to the
+    cell).  The CSR must be **block diagonal over the graphs** -- both ends of every edge with
+    the same ``seg_id``, as in every ``GraphBatch``: the offset of an edge is defined by the cell
+    of its destination row, and the kernel reads the out-edges of a node with the node's own
+    cell (``CGNN_CHECK`` verifies it)."""
+    n, ldp, lanes, nnz = _pair_args("pair_d2_pbc_bwd", rowptr, col, pos, D, lanes, nnz)
+    _pair_pbc_args("pair_d2_pbc_bwd", n, shift, nnz, cell, seg_id, pos.is_cuda)
+    if n != pos.shape[0] or rowptr_t.numel() != n + 1:
+        raise ValueError("pair_d2_pbc_bwd: a square CSR over the %d positions expected (%d rows, %d transposed rows)"
+                         % (pos.shape[0], n, rowptr_t.numel() - 1))
+    if g.dim() != 1 or g.numel() < nnz or col_t.numel() < nnz or eperm_t.numel() < nnz:
+        raise ValueError("pair_d2_pbc_bwd: g, col_t and eperm_t must hold %d edges" % nnz)
+    if out is None:
+        out = torch.empty_like(pos)
+    if out.shape != pos.shape:
+        raise ValueError("pair_d2_pbc_bwd: out must be %s like pos, got %s" % (tuple(pos.shape), tuple(out.shape)))
+    if checks.enabled():
+        checks.csr(rowptr_t, col_t, n, "pair_d2_pbc_bwd (transposed)")
+        checks.index(eperm_t[:nnz], max(nnz, 1), "pair_d2_pbc_bwd eperm_t")
+        ends = _row_ids(rowptr)
+        if not torch.equal(seg_id[ends.long()], seg_id[col[:ends.numel()].long()]):
+            raise ValueError("CGNN_CHECK: pair_d2_pbc_bwd: an edge joins two graphs (seg_id of its ends differ)")
+    if n == 0 or nnz == 0:
+        return out.zero_()
+    if pos.is_cuda:
+        _seg_gpu_operands("pair_d2_pbc_bwd", (("rowptr", rowptr), ("col", col), ("rowptr_t", rowptr_t),
+                                              ("col_t", col_t), ("eperm_t", eperm_t)), (("g", g), ("out", out)), ())
+        native.hip().gnn_pair_d2_pbc_bwd(rowptr.data_ptr(), col.data_ptr(), shift.data_ptr(), rowptr_t.data_ptr(),
+                                         col_t.data_ptr(), eperm_t.data_ptr(), pos.data_ptr(), cell.data_ptr(),
+                                         seg_id.data_ptr(), g.data_ptr(), out.data_ptr(), n, nnz, cell.shape[0],
+                                         int(D), ldp, lanes, _st(pos))
+        return out
+    D = int(D)
+    at = _acc_dtype(pos.dtype)
+    rows = _row_ids(rowptr)
+    E = rows.numel()
+    src = col[:E].long()
+    p = pos[:, :D].to(at)
+    w = g[:E].to(at)[:, None] * (p[rows] - (p[src] + _edge_offsets(rows, shift, cell, seg_id, D, at)))
     acc = torch.zeros(n, D, dtype=at).index_add_(0, rows, w).index_add_(0, src, -w)
     out.zero_()
     out[:, :D] = (2 * acc).to(out.dtype)

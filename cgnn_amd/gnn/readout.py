@@ -52,7 +52,14 @@ class GraphBatch:
     rows at construction: ``cptr`` (int32 ``[C + 1]``, the row boundaries of the chunks),
     ``gchunk`` (int32 ``[G + 1]``, the chunks of each graph), ``n_chunks`` and ``single_pass``
     (no graph is longer than a chunk).  Graph lengths 70, 0, 10 with chunks of 64 rows give
-    ``cptr = [0, 64, 70, 80]`` and ``gchunk = [0, 2, 2, 3]``."""
+    ``cptr = [0, 64, 70, 80]`` and ``gchunk = [0, 2, 2, 3]``.
+
+    A periodic ``geometry.radius_graph`` also sets ``shift`` (int32 ``[nnz]``, the lattice image
+    of each edge's source: byte a = ``s[a]`` as an int8, 0 = the home image) and ``cell`` (fp32
+    ``[G, 9]``, row-major 3 x 3 per graph); both are ``None`` otherwise."""
+
+    shift = None
+    cell = None
 
     def __init__(self, gptr: torch.Tensor, rowptr: Optional[torch.Tensor] = None, col: Optional[torch.Tensor] = None,
                  eperm: Optional[torch.Tensor] = None, chunk: Optional[int] = None):
@@ -95,6 +102,9 @@ class GraphBatch:
     def _move(self, device):
         for name in self._TENSORS:
             setattr(self, name, getattr(self, name).to(device))
+        for name in ("shift", "cell"):
+            if getattr(self, name) is not None:
+                setattr(self, name, getattr(self, name).to(device))
         return self
 
     @classmethod
@@ -133,7 +143,16 @@ class GraphBatch:
     def to(self, device) -> "GraphBatch":
         """A copy on ``device`` (the same chunk size)."""
         b = GraphBatch(self.gptr, self.rowptr, self.col, self.eperm, chunk=self.chunk)
+        b.shift, b.cell = self.shift, self.cell
         return b._move(torch.device(device))
+
+    def shifts(self):
+        """The lattice image of each edge's source, int32 ``[nnz, 3]``, unpacked from ``shift``:
+        edge e of row i joins ``pos[i]`` and ``pos[col[e]] + shifts()[e] @ cell[g]``.  Only for a
+        periodic ``geometry.radius_graph``."""
+        if self.shift is None:
+            raise ValueError("GraphBatch.shifts: not a periodic graph (no cell was given)")
+        return ops.unpack_shift(self.shift, 3)
 
     def transposed_perm(self):
         """``(rowptr_t, col_t, eperm)`` of the transposed CSR, as ``WeightedGraph.transposed``

@@ -45,8 +45,12 @@ class SchNet(torch.nn.Module):
     softplus between.  ``z``: atomic numbers in ``[0, max_z)``.  The embedding rows are standard
     normal, the dense layers Glorot-uniform with zero biases, all drawn from ``generator``.
 
-    Out of scope: training on forces (a double backward through ``pair_distance``) and
-    periodic cells."""
+    Periodic systems: ``neighbors``, ``forward`` and ``energy_and_forces`` take ``cell=`` / ``pbc=``
+    as ``radius_graph`` does (positions inside the cell: ``geometry.wrap_positions``); an atom then
+    interacts with the lattice images of the others and of itself.
+
+    Out of scope: training on forces (a double backward through ``pair_distance``), the
+    gradient with respect to the cell (stress) and ``max_num_neighbors`` over periodic images."""
 
     def __init__(self, hidden: int = 128, n_filters: int = 128, n_interactions: int = 3, n_gaussians: int = 50,
                  cutoff: float = 5.0, max_z: int = 100, generator: Optional[torch.Generator] = None,
@@ -63,20 +67,22 @@ class SchNet(torch.nn.Module):
         self.out1 = _Dense(hidden, hidden // 2, generator=generator)
         self.out2 = _Dense(hidden // 2, 1, generator=generator)
 
-    def neighbors(self, pos: torch.Tensor, batch: Union[GraphBatch, torch.Tensor, None] = None) -> GraphBatch:
+    def neighbors(self, pos: torch.Tensor, batch: Union[GraphBatch, torch.Tensor, None] = None,
+                  cell: Optional[torch.Tensor] = None, pbc=True) -> GraphBatch:
         """The radius graph of the model's cutoff, capped at the ``max_num_neighbors`` nearest
-        (one host sync: ``radius_graph``)."""
-        return radius_graph(pos, self.cutoff, batch, max_num_neighbors=self.max_num_neighbors)
+        (one host sync: ``radius_graph``); with ``cell`` the periodic one."""
+        return radius_graph(pos, self.cutoff, batch, max_num_neighbors=self.max_num_neighbors, cell=cell, pbc=pbc)
 
     def forward(self, z: torch.Tensor, pos: torch.Tensor, batch: Union[GraphBatch, torch.Tensor, None] = None,
-                graph: Optional[GraphBatch] = None) -> torch.Tensor:
+                graph: Optional[GraphBatch] = None, cell: Optional[torch.Tensor] = None, pbc=True) -> torch.Tensor:
         """The energy of each graph, ``[n_graphs]``.  ``z`` integer ``[n]``, ``pos`` ``[n, D]``;
-        ``batch`` as in ``radius_graph``.  ``graph``: a neighbour list from ``neighbors`` to
-        reuse (``batch`` is then ignored)."""
+        ``batch``, ``cell`` and ``pbc`` as in ``radius_graph``.  ``graph``: a neighbour list from
+        ``neighbors`` to reuse (``batch``, ``cell`` and ``pbc`` are then ignored: a periodic list
+        carries its cell)."""
         if z.dim() != 1 or z.shape[0] != pos.shape[0] or z.is_floating_point():
             raise ValueError("SchNet: z must be an integer vector [%d], got %s %s"
                              % (pos.shape[0], z.dtype, tuple(z.shape)))
-        g = self.neighbors(pos, batch) if graph is None else graph
+        g = self.neighbors(pos, batch, cell, pbc) if graph is None else graph
         d = pair_distance(pos, g)
         e = self.smearing(d)
         c = cosine_cutoff(d, self.cutoff)
@@ -87,11 +93,12 @@ class SchNet(torch.nn.Module):
         return graph_readout(y, g, "sum")[:, 0]
 
     def energy_and_forces(self, z: torch.Tensor, pos: torch.Tensor,
-                          batch: Union[GraphBatch, torch.Tensor, None] = None, graph: Optional[GraphBatch] = None):
+                          batch: Union[GraphBatch, torch.Tensor, None] = None, graph: Optional[GraphBatch] = None,
+                          cell: Optional[torch.Tensor] = None, pbc=True):
         """``(E [n_graphs], F [n, D])`` with ``F = -dE/dpos`` through ``torch.autograd.grad``.
         The parameters receive no gradient and the force is not differentiable."""
         p = pos.detach().requires_grad_(True)
         with torch.enable_grad():
-            E = self.forward(z, p, batch, graph)
+            E = self.forward(z, p, batch, graph, cell, pbc)
             dpos, = torch.autograd.grad(E.sum(), p)
         return E.detach(), -dpos
