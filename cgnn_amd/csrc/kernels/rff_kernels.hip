@@ -446,7 +446,7 @@ static int rff_fb_d(int mode, const float* xhat, const float* data, const float*
   const bool whole = (size_t)F * (D + 2) <= cap;
   const int FC = whole ? F : (int)(cap / (D + 2)) / 32 * 32;
   if (D > 64 || (!force_valu && whole)) {    // the vector kernels stop at D = 64
-    if (FC < 32) return -2;
+    if (!whole && FC < 32) return -2;        // a whole image may hold fewer than 32 features (k <= 4)
     const size_t glds = sizeof(float) * (size_t)FC * (D + 2);
     hipLaunchKernelGGL((rff_mfma_feat_kernel<D>), dim3((F + 255) / 256, R), dim3(512), 0, st, xhat, data, W, diff,
                        loss_part, N, F, norm);
