@@ -239,6 +239,36 @@ int gnn_launch_pair_d2_pbc_bwd(const int* rowptr, const int* col, const int* shi
                                const int* seg_id, const float* g, float* dpos, int n, int nnz, int G, int D, int ldp,
                                int lanes, hipStream_t st);
 
+// ---- gnn_cells.hip: the cell-list radius search, equal to radius_count / radius_fill bit for
+// bit (the contract, the grid and its error argument: the file's header).  cells_grid writes
+// the grid of every graph, glo fp32 [G, 8] = lo[3], scale[3], 0, 0 and gn int32 [G, 4] = n_0,
+// n_1, n_2, their product, with part = gnn_cells_grid_floats(n) floats of scratch; cells_bin
+// cell_id [n], a global cell id in [0, n + G) or the sentinel n + G.  The caller sorts the
+// points by cell_id (stable): perm [n] the point at each sorted position, scell [n] its cell,
+// cptr [n + G + 2] the first sorted position of each cell id, spos fp32 [n, 4] the positions
+// in that order (ldp must be 4).  cells_count writes deg [n] under the original row ids;
+// cells_fill the rows in scan order into the scratch list sj / sd [cap] at rowptr[i] ..
+// rowptr[i + 1]; cells_rows col (and d2, which may be null) [cap] = every scratch row in
+// ascending source id.  Nothing is written at or past cap.  Checks in this order: -1 D outside
+// 1..3 or a lanes value that is not compiled; -3 ldp < D (spos: ldp != 4), cap < 0, or an r
+// that is negative or not finite; 0 without a launch for n <= 0 (and cap == 0 in fill and
+// rows; cells_grid then leaves glo / gn to the caller); -3 a required pointer missing (every
+// pointer but cells_rows' d2) or G < 1; -4 the grid would overflow.  lanes = 0: the search's
+// default width (count, fill), from cap / n (rows)
+int gnn_cells_grid_floats(int n);
+int gnn_launch_cells_grid(const float* pos, const int* gptr, float* part, float* glo, int* gn, int n, int G, int D,
+                          int ldp, float r, hipStream_t st);
+int gnn_launch_cells_bin(const float* pos, const int* gptr, const int* seg_id, const float* glo, const int* gn,
+                         int* cell_id, int n, int G, int D, int ldp, hipStream_t st);
+int gnn_launch_cells_count(const float* spos, const int* perm, const int* scell, const int* cptr, const int* gptr,
+                           const int* seg_id, const int* gn, int* deg, int n, int G, int D, int ldp, float r, int loop,
+                           int lanes, hipStream_t st);
+int gnn_launch_cells_fill(const float* spos, const int* perm, const int* scell, const int* cptr, const int* gptr,
+                          const int* seg_id, const int* gn, const int* rowptr, int* sj, float* sd, int n, int G, int D,
+                          int ldp, float r, int loop, int lanes, int cap, hipStream_t st);
+int gnn_launch_cells_rows(const int* rowptr, const int* sj, const float* sd, int* col, float* d2, int n, int cap,
+                          int lanes, hipStream_t st);
+
 // ---- gnn_edge_softmax.hip: softmax over each row's edges and its gradient.  s / p / dp / ds
 // are fp32, head-major [K, ld] (head k's edge e at k * ld + e); p may alias s and ds may
 // alias dp.  lanes: the sub-group width, 0 = from nnz / n_rows.  -3: a required pointer

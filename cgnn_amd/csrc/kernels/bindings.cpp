@@ -318,6 +318,49 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("pos"), py::arg("gptr"), py::arg("seg_id"), py::arg("rowptr"), py::arg("tau_d2"), py::arg("tau_j"),
      py::arg("col"), py::arg("d2"), py::arg("n"), py::arg("n_graphs"), py::arg("D"), py::arg("ld_pos"),
      py::arg("loop"), py::arg("lanes"), py::arg("st"));
+  // the cell-list radius search (gnn_cells.hip)
+  m.def("gnn_cells_grid_floats", [](int n) { return gnn_cells_grid_floats(n); }, py::arg("n"));
+  m.def("gnn_cells_grid", [](uint64_t pos, uint64_t gptr, uint64_t part, uint64_t glo, uint64_t gn, int n,
+                             int n_graphs, int D, int ld_pos, float r, uint64_t st) {
+    chk(gnn_launch_cells_grid(Pt<const float>(pos), Pt<const int>(gptr), Pt<float>(part), Pt<float>(glo), Pt<int>(gn),
+                              n, n_graphs, D, ld_pos, r, S(st)),
+        "gnn_cells_grid");
+  }, py::arg("pos"), py::arg("gptr"), py::arg("part"), py::arg("glo"), py::arg("gn"), py::arg("n"),
+     py::arg("n_graphs"), py::arg("D"), py::arg("ld_pos"), py::arg("r"), py::arg("st"));
+  m.def("gnn_cells_bin", [](uint64_t pos, uint64_t gptr, uint64_t seg_id, uint64_t glo, uint64_t gn, uint64_t cell_id,
+                            int n, int n_graphs, int D, int ld_pos, uint64_t st) {
+    chk(gnn_launch_cells_bin(Pt<const float>(pos), Pt<const int>(gptr), Pt<const int>(seg_id), Pt<const float>(glo),
+                             Pt<const int>(gn), Pt<int>(cell_id), n, n_graphs, D, ld_pos, S(st)),
+        "gnn_cells_bin");
+  }, py::arg("pos"), py::arg("gptr"), py::arg("seg_id"), py::arg("glo"), py::arg("gn"), py::arg("cell_id"),
+     py::arg("n"), py::arg("n_graphs"), py::arg("D"), py::arg("ld_pos"), py::arg("st"));
+  m.def("gnn_cells_count", [](uint64_t spos, uint64_t perm, uint64_t scell, uint64_t cptr, uint64_t gptr,
+                              uint64_t seg_id, uint64_t gn, uint64_t deg, int n, int n_graphs, int D, int ld_pos,
+                              float r, int loop, int lanes, uint64_t st) {
+    chk(gnn_launch_cells_count(Pt<const float>(spos), Pt<const int>(perm), Pt<const int>(scell), Pt<const int>(cptr),
+                               Pt<const int>(gptr), Pt<const int>(seg_id), Pt<const int>(gn), Pt<int>(deg), n,
+                               n_graphs, D, ld_pos, r, loop, lanes, S(st)),
+        "gnn_cells_count");
+  }, py::arg("spos"), py::arg("perm"), py::arg("scell"), py::arg("cptr"), py::arg("gptr"), py::arg("seg_id"),
+     py::arg("gn"), py::arg("deg"), py::arg("n"), py::arg("n_graphs"), py::arg("D"), py::arg("ld_pos"), py::arg("r"),
+     py::arg("loop"), py::arg("lanes"), py::arg("st"));
+  m.def("gnn_cells_fill", [](uint64_t spos, uint64_t perm, uint64_t scell, uint64_t cptr, uint64_t gptr,
+                             uint64_t seg_id, uint64_t gn, uint64_t rowptr, uint64_t sj, uint64_t sd, int n,
+                             int n_graphs, int D, int ld_pos, float r, int loop, int lanes, int cap, uint64_t st) {
+    chk(gnn_launch_cells_fill(Pt<const float>(spos), Pt<const int>(perm), Pt<const int>(scell), Pt<const int>(cptr),
+                              Pt<const int>(gptr), Pt<const int>(seg_id), Pt<const int>(gn), Pt<const int>(rowptr),
+                              Pt<int>(sj), Pt<float>(sd), n, n_graphs, D, ld_pos, r, loop, lanes, cap, S(st)),
+        "gnn_cells_fill");
+  }, py::arg("spos"), py::arg("perm"), py::arg("scell"), py::arg("cptr"), py::arg("gptr"), py::arg("seg_id"),
+     py::arg("gn"), py::arg("rowptr"), py::arg("sj"), py::arg("sd"), py::arg("n"), py::arg("n_graphs"), py::arg("D"),
+     py::arg("ld_pos"), py::arg("r"), py::arg("loop"), py::arg("lanes"), py::arg("cap"), py::arg("st"));
+  m.def("gnn_cells_rows", [](uint64_t rowptr, uint64_t sj, uint64_t sd, uint64_t col, uint64_t d2, int n, int cap,
+                             int lanes, uint64_t st) {
+    chk(gnn_launch_cells_rows(Pt<const int>(rowptr), Pt<const int>(sj), Pt<const float>(sd), Pt<int>(col),
+                              Pt<float>(d2), n, cap, lanes, S(st)),
+        "gnn_cells_rows");
+  }, py::arg("rowptr"), py::arg("sj"), py::arg("sd"), py::arg("col"), py::arg("d2"), py::arg("n"), py::arg("cap"),
+     py::arg("lanes"), py::arg("st"));
   // the same over periodic cells: image-shift radius search, shifted pair distances (gnn_geometry.hip)
   m.def("gnn_radius_pbc_count", [](uint64_t pos, uint64_t gptr, uint64_t seg_id, uint64_t cell, uint64_t nimg,
                                    uint64_t deg, int n, int n_graphs, int D, int ld_pos, float r, int loop, int lanes,

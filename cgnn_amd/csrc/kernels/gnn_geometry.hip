@@ -17,7 +17,8 @@
 // D <= c < ldp are never read.  graph(i) = [gptr[seg_id[i]], gptr[seg_id[i] + 1]) (gptr int32
 // [G + 1], seg_id int32 [n]: GraphBatch.gptr / .batch).
 //
-// The squared distance, one definition for every kernel of this file (sq_dist):
+// The squared distance, one definition for every kernel of this file and of gnn_cells.hip
+// (sq_dist, gnn_point.h):
 //   dx = p_i[0] - p_j[0], dy = p_i[1] - p_j[1], dz = p_i[2] - p_j[2]     each one fp32 subtract
 //   d2 = fma(dz, dz, fma(dy, dy, dx * dx))                                explicit, no contraction
 // with the terms of absent coordinates dropped (D = 2: fma(dy, dy, dx * dx); D = 1: dx * dx).
@@ -26,7 +27,9 @@
 // Contract of the search.  r2 = r * r is one fp32 product, made on the host.  The boundary is
 // inclusive (d2 <= r2); a NaN d2 is not an edge (the compare is false); coincident points are
 // neighbours.  The search is brute force inside each graph, O(n_g^2): the algorithm for
-// molecules and other graphs of up to a few thousand points.  No cell lists, no k-NN in
+// molecules and other graphs of up to a few thousand points.  Large point clouds: the
+// cell-list search of gnn_cells.hip, which returns this file's CSR bit for bit (radius search
+// only, no periodic cells, no k-NN or neighbour cap there).  No k-NN in
 // feature space (D > 3); periodic cells: the radius search only ("Periodic cells" below), no
 // k-NN or neighbour cap over images, no gradient with respect to the cell.
 //
@@ -133,54 +136,18 @@
 #include "cgnn_common.h"
 #include "cgnn_api.h"
 #include "gnn_launch.h"
+#include "gnn_point.h"
 #include <algorithm>
 #include <climits>
 #include <cmath>
 
 using namespace cgnn;
+using namespace cgnn::geo;
 using namespace cgnn::launch;
 
 namespace {
 
-template <int D>
-struct Point {
-  float c[D];
-};
-
-template <int D>
-__device__ __forceinline__ Point<D> load_point(const float* __restrict__ pos, int i, int ldp) {
-  Point<D> p;
-  const float* q = pos + (size_t)i * ldp;
-#pragma unroll
-  for (int c = 0; c < D; ++c) p.c[c] = q[c];
-  return p;
-}
-
-template <int D>
-__device__ __forceinline__ float sq_dist(const Point<D>& a, const Point<D>& b) {
-  const float dx = __fsub_rn(a.c[0], b.c[0]);
-  float d2 = __fmul_rn(dx, dx);
-  if (D > 1) {
-    const float dy = __fsub_rn(a.c[D > 1 ? 1 : 0], b.c[D > 1 ? 1 : 0]);
-    d2 = __fmaf_rn(dy, dy, d2);
-  }
-  if (D > 2) {
-    const float dz = __fsub_rn(a.c[D > 2 ? 2 : 0], b.c[D > 2 ? 2 : 0]);
-    d2 = __fmaf_rn(dz, dz, d2);
-  }
-  return d2;
-}
-
-// the row of this sub-group and its lane in it
-template <int L>
-__device__ __forceinline__ long sub_row(int& sub, int& sl) {
-  constexpr int RPW = 64 / L;
-  const int lane = threadIdx.x & 63;
-  sub = lane / L;
-  sl = lane - sub * L;
-  const unsigned blk = xcd_remap(blockIdx.x, gridDim.x);
-  return ((long)blk * (blockDim.x >> 6) + (threadIdx.x >> 6)) * RPW + sub;
-}
+// Point, load_point, sq_dist, sub_row: gnn_point.h, shared with gnn_cells.hip
 
 template <int L>
 __device__ __forceinline__ float group_sum(float v) {

@@ -20,9 +20,16 @@ arguments of ``layers.CFConv``:
 * ``GaussianSmearing`` / ``cosine_cutoff`` -- SchNet's radial basis and cutoff envelope, plain
   PyTorch: elementwise on ``[nnz, K]``.
 
-Limits.  The search is brute force inside each graph, O(n_g^2): right for molecules and other
-graphs of up to a few thousand points.  There are no cell lists for one large point cloud and
-no k-NN in feature space (``D > 3``).  Periodic cells: the radius search only (no k-NN and no
+* cell lists -- ``radius_graph(..., method="cells")``, and ``"auto"`` for graphs of at least
+  ``_CELLS_MIN_POINTS`` points: the binned search for large point clouds (``ops.cells_grid`` /
+  ``cells_bin`` / ``cells_order`` / ``cells_count`` / ``cells_fill``), O(n) instead of O(n_g^2) and
+  the brute-force graph bit for bit.
+
+Limits.  Below ``_CELLS_MIN_POINTS`` the search is brute force inside each graph, O(n_g^2):
+right for molecules and other graphs of up to a few thousand points.  The cell lists serve the
+plain radius search only: no periodic cells, no k-NN and no neighbour cap on the cell path
+(those stay brute force), ``D <= 3``; no k-NN in feature space (``D > 3``).  Periodic cells: the
+radius search only (no k-NN and no
 neighbour cap over images), at most ``ops.PBC_NIMG_MAX`` images per direction, no gradient
 with respect to the cell (stress).  ``pair_distance`` is differentiable once: a double backward
 (training on forces) is not implemented.
@@ -48,6 +55,14 @@ def _auto_lanes(max_count: int) -> int:
             return L
     return 64
 
+
+_METHODS = ("auto", "brute", "cells")
+
+# method = "auto": the longest graph from which radius_graph takes the cell lists.  The
+# measured crossover -- one cloud of 8192 points: brute force 105 us, cells 124 us; 16384
+# points: 353 us against 110 us (docs/PERF.md, "Cell lists") -- rounded up to a power of two,
+# and never below 4096: every shape measured on the brute-force kernels stays on them.
+_CELLS_MIN_POINTS = 16384
 
 _KNN_WAVES = 4096       # waves that keep the select pass busy: four per SIMD of an MI355X
 
@@ -183,7 +198,8 @@ def wrap_positions(pos: torch.Tensor, cell: torch.Tensor, pbc=True,
 
 def radius_graph(pos: torch.Tensor, r: float, batch: Union[GraphBatch, torch.Tensor, None] = None,
                  loop: bool = False, lanes: Optional[int] = None,
-                 max_num_neighbors: Optional[int] = None, cell: Optional[torch.Tensor] = None, pbc=True) -> GraphBatch:
+                 max_num_neighbors: Optional[int] = None, cell: Optional[torch.Tensor] = None, pbc=True,
+                 method: str = "auto") -> GraphBatch:
     """The graph of all pairs of points of the same graph at most ``r`` apart.
 
     ``pos`` is ``[n, D]``, ``D`` in 1..3.  ``batch``: a ``GraphBatch`` (its ``gptr`` / ``batch``
@@ -222,8 +238,23 @@ def radius_graph(pos: torch.Tensor, r: float, batch: Union[GraphBatch, torch.Ten
     raises ``NotImplementedError``; a cutoff that needs more than ``ops.PBC_NIMG_MAX`` images
     along an axis raises (``image_ranges``).
 
-    Brute force inside each graph, O(n_g^2) (times the number of images): for molecules,
-    crystal cells and graphs of up to a few thousand points.  No cell lists."""
+    ``method``: ``"brute"`` searches every pair of a graph, O(n_g^2) (times the number of
+    images): for molecules, crystal cells and graphs of up to a few thousand points.
+    ``"cells"`` bins every graph into a grid of cells at least ``r`` wide, built on the device
+    from its bounding box, and searches the neighbouring cells only (``ops.cells_grid`` /
+    ``cells_bin`` / ``cells_order`` / ``cells_count`` / ``cells_fill``): O(n) for a point cloud of
+    bounded density, and **the same** ``GraphBatch`` **bit for bit** (``rowptr``, ``col``, ``d2``,
+    ``eperm``); still one host synchronisation, a handful of launches more and one scratch copy of
+    the edge list.  ``"auto"`` (the default) takes the cells when the longest graph has at least
+    ``_CELLS_MIN_POINTS`` points (docs/PERF.md, "Cell lists") and the brute search below.  The
+    cell path is the plain radius search: together with ``cell=`` or ``max_num_neighbors=``
+    ``"cells"`` raises ``NotImplementedError``, and ``"auto"`` leaves those two on their own
+    (brute-force) paths.  Its default ``lanes`` does not depend on the graph lengths."""
+    if method not in _METHODS:
+        raise ValueError("radius_graph: method must be one of %s, got %r" % (_METHODS, method))
+    if method == "cells" and (cell is not None or max_num_neighbors is not None):
+        raise NotImplementedError("radius_graph: method = 'cells' searches neither periodic images (cell=) nor the "
+                                  "nearest neighbours (max_num_neighbors=)")
     if cell is not None:
         if max_num_neighbors is not None:
             raise NotImplementedError("radius_graph: max_num_neighbors over periodic images is not implemented")
@@ -234,16 +265,26 @@ def radius_graph(pos: torch.Tensor, r: float, batch: Union[GraphBatch, torch.Ten
     p = pos.detach().contiguous()
     n, D = p.shape
     out = _graphs_of("radius_graph", p, batch)
-    L = _auto_lanes(out.max_count) if lanes is None else lanes
-    deg = ops.radius_count(p, D, r, out.gptr, out.batch, loop=loop, lanes=L)
+    cells = method == "cells" or (method == "auto" and out.max_count >= _CELLS_MIN_POINTS)
+    if cells:
+        # grid, bins and cell order: launches and device plumbing, no read-back
+        _, gn, _, perm, scell, cptr, spos = ops.cells_prepare(p, D, r, out.gptr, out.batch)
+        deg = ops.cells_count(spos, perm, scell, cptr, out.gptr, out.batch, gn, D, r, loop=loop, lanes=lanes)
+    else:
+        L = _auto_lanes(out.max_count) if lanes is None else lanes
+        deg = ops.radius_count(p, D, r, out.gptr, out.batch, loop=loop, lanes=L)
     rp = torch.zeros(n + 1, dtype=torch.int64, device=p.device)
     rp[1:] = torch.cumsum(deg, 0, dtype=torch.int64)
     nnz = int(rp[-1])                                         # the one host sync
     if nnz >= 2 ** 31:
         raise ValueError("radius_graph: %d edges do not fit int32" % nnz)
     out.rowptr = rp.to(torch.int32)
-    out.col, out.d2 = ops.radius_fill(p, D, r, out.gptr, out.batch, out.rowptr, loop=loop, lanes=L, nnz=nnz,
-                                      with_d2=True)
+    if cells:
+        out.col, out.d2 = ops.cells_fill(spos, perm, scell, cptr, out.gptr, out.batch, gn, D, r, out.rowptr, loop=loop,
+                                         lanes=lanes, nnz=nnz, with_d2=True)
+    else:
+        out.col, out.d2 = ops.radius_fill(p, D, r, out.gptr, out.batch, out.rowptr, loop=loop, lanes=L, nnz=nnz,
+                                          with_d2=True)
     out.eperm = torch.arange(nnz, dtype=torch.int64, device=p.device)
     out._tperm = None
     return out

@@ -5,7 +5,8 @@ models run in CI); on a GPU the HIP kernels of csrc/kernels/gnn_sparse.hip (and
 gnn_wspmm.hip for the edge-weighted ops, gnn_pool.hip for max / min pooling,
 gnn_edge_softmax.hip for the softmax over a node's edges, gnn_espmm.hip for the aggregate
 with a feature row per edge, gnn_readout.hip for the reduction of each graph's node rows
-and its reverse, gnn_geometry.hip for the radius-graph and k-NN searches and the pair distances) are mandatory -- a missing extension raises instead of silently falling back.
+and its reverse, gnn_geometry.hip for the radius-graph and k-NN searches and the pair distances,
+gnn_cells.hip for the cell-list radius search of large point clouds) are mandatory -- a missing extension raises instead of silently falling back.
 """
 from __future__ import annotations
 
@@ -831,8 +832,10 @@ def radius_count(pos, D, r, gptr, seg_id, loop=False, lanes=None, out=None):
     ``d2 = fma(dz, dz, fma(dy, dy, dx * dx))`` of fp32 differences and ``r * r`` is one fp32
     product; the boundary is inclusive, a NaN distance is no edge, coincident points are
     neighbours.  Brute force inside each graph, O(n_g^2) -- for molecules and other graphs of
-    up to a few thousand points: no cell lists (``knn_select`` / ``knn_fill`` cap a row at its k
-    nearest; ``radius_pbc_count`` / ``radius_pbc_fill`` search the images of a periodic cell).
+    up to a few thousand points; ``cells_count`` / ``cells_fill`` are the cell-list search for
+    large point clouds, with this op's result bit for bit (``knn_select`` / ``knn_fill`` cap a row
+    at its k nearest; ``radius_pbc_count`` / ``radius_pbc_fill`` search the images of a periodic
+    cell: both brute force only).
     ``lanes``: force the sub-group width (8 / 16 / 32 / 64; default from ``n / G``); the
     result is the same for every width.  ``out``: a preallocated ``deg``.  CPU tensors: PyTorch
     with the same contract."""
@@ -905,6 +908,309 @@ def _fill_rows(deg, col, dd, rowptr, out, d2):
     out[slot[ok]] = col[ok].to(out.dtype)
     if d2 is not None:
         d2[slot[ok]] = dd[ok].to(d2.dtype)
+
+
+CELLS_NA_MAX = 1024     # cells per axis (gnn_cells.hip: the cap its error argument needs)
+_CELLS_SIDE = 1.0 + 2.0 ** -10          # the least cell side is r * (1 + 2^-10) ...
+_CELLS_SIDE_MIN = 2.0 ** -60            # ... and at least this (r = 0, squares that underflow)
+_CELLS_EXT_MAX = 2.0 ** 100             # a longer axis has one cell
+
+
+def _cells_tables(what, G, glo, gn, on_gpu):
+    if glo.shape != (G, 8) or gn.shape != (G, 4):
+        raise ValueError("%s: glo must be [%d, 8] and gn [%d, 4], got %s and %s"
+                         % (what, G, G, tuple(glo.shape), tuple(gn.shape)))
+    if on_gpu:
+        _seg_gpu_operands(what, (("gn", gn),), (("glo", glo),), ())
+    elif gn.dtype != torch.int32:
+        raise TypeError("%s: gn must be int32, got %s" % (what, gn.dtype))
+
+
+def cells_grid(pos, D, r, gptr, glo=None, gn=None, part=None):
+    """The grid of every graph for the cell-list radius search (gnn_cells.hip, cells_part_kernel
+    / cells_grid_kernel): ``glo`` fp32 ``[G, 8]`` = ``lo[3]``, ``scale[3]``, 0, 0 and ``gn`` int32
+    ``[G, 4]`` = ``n_0, n_1, n_2`` and their product, from the finite points of each graph
+    ``[gptr[g], gptr[g+1])`` and ``r`` alone, on the device, with no read-back.  Along axis a:
+    ``lo`` the least coordinate, ``ext = hi - lo``, ``n_a = min(1024, int(ext / s0))`` cells with
+    ``s0 = max(r * (1 + 2^-10), 2^-60)``, one cell when ``ext`` is below ``2 s0``, zero, not
+    finite or above ``2^100``; then the largest ``n_a`` (the lowest axis among equals) is halved,
+    rounding up, until the graph has at most ``max(1, n_g)`` cells; ``scale = n_a / ext`` (0 for
+    one cell).  ``bin_a(x) = min(n_a - 1, int((x - lo) * scale))`` is monotone in ``x``, and two
+    points the radius search connects lie in cells that differ by at most one along every axis
+    (the argument, in fp32 error terms: the header of gnn_cells.hip).  A graph with one cell is
+    the brute-force search.  ``r = 0`` is legal.  ``glo`` / ``gn``: preallocated outputs;
+    ``part``: fp32 scratch of ``8 * ceil(n / 1024)`` values on the GPU.  CPU tensors: PyTorch with
+    the same arithmetic (fp64 positions: in fp64).  Returns ``(glo, gn)``."""
+    n, ldp, _ = _geo_args("cells_grid", pos, D, None)
+    D = int(D)
+    r = float(r)
+    if not (r >= 0 and r < float("inf")):
+        raise ValueError("cells_grid: r must be finite and not negative, got %r" % r)
+    if gptr.dim() != 1 or gptr.numel() < 2 and n:
+        raise ValueError("cells_grid: gptr must be a vector [G + 1] with G >= 1")
+    G = gptr.numel() - 1
+    at = _acc_dtype(pos.dtype)
+    if glo is None:
+        glo = torch.empty(G, 8, dtype=at, device=pos.device)
+    if gn is None:
+        gn = torch.empty(G, 4, dtype=torch.int32, device=pos.device)
+    _cells_tables("cells_grid", G, glo, gn, pos.is_cuda)
+    if n == 0:
+        glo.zero_()
+        gn.fill_(1)
+        return glo, gn
+    if pos.is_cuda:
+        need = native.hip().gnn_cells_grid_floats(n)
+        if part is None:
+            part = torch.empty(need, dtype=torch.float32, device=pos.device)
+        if part.numel() < need:
+            raise ValueError("cells_grid: part holds %d values, %d needed" % (part.numel(), need))
+        _seg_gpu_operands("cells_grid", (("gptr", gptr),), (("part", part),), ())
+        native.hip().gnn_cells_grid(pos.data_ptr(), gptr.data_ptr(), part.data_ptr(), glo.data_ptr(), gn.data_ptr(),
+                                    n, G, D, ldp, r, _st(pos))
+        return glo, gn
+    s0 = torch.maximum(torch.tensor(r, dtype=at) * torch.tensor(_CELLS_SIDE, dtype=at),
+                       torch.tensor(_CELLS_SIDE_MIN, dtype=at))
+    glo.zero_()
+    gn.fill_(1)
+    gp = gptr.tolist()
+    for g in range(G):
+        g0 = min(max(gp[g], 0), n)
+        g1 = min(max(gp[g + 1], g0), n)
+        p = pos[g0:g1, :D].to(at)
+        p = p[torch.isfinite(p).all(1)]
+        if p.shape[0] == 0:
+            continue
+        lo, hi = p.min(0).values, p.max(0).values
+        ext = hi - lo                                         # inf when it overflows
+        na = [1, 1, 1]
+        for a in range(D):
+            if 0 < float(ext[a]) <= _CELLS_EXT_MAX:
+                q = int(torch.clamp(ext[a] / s0, max=float(CELLS_NA_MAX)))
+                if q >= 2:
+                    na[a] = q
+        cap = max(g1 - g0, 1)
+        while na[0] * na[1] * na[2] > cap:
+            a = max(range(3), key=lambda c: (na[c], -c))       # the largest, the lowest axis among equals
+            na[a] = (na[a] + 1) // 2
+        glo[g, :D] = lo
+        for a in range(D):
+            if na[a] >= 2:
+                glo[g, 3 + a] = torch.tensor(na[a], dtype=at) / ext[a]
+        gn[g] = torch.tensor(na + [na[0] * na[1] * na[2]], dtype=torch.int32)
+    return glo, gn
+
+
+def cells_bin(pos, D, gptr, seg_id, glo, gn, out=None):
+    """The cell of every point (gnn_cells.hip, cells_bin_kernel): ``cell_id`` int32 ``[n]``,
+    ``gptr[g] + g + (bin_0 n_1 + bin_1) n_2 + bin_2`` with ``g = seg_id[i]`` and the bins of
+    ``cells_grid`` (absent axes: one cell) -- the cells of graph g fill the id range
+    ``[gptr[g] + g, gptr[g+1] + g + 1)`` -- or the sentinel ``n + G`` for a point with a NaN or
+    inf coordinate, a ``seg_id`` outside ``[0, G)`` or one that names another graph's range: such
+    a point has an empty row and is nobody's neighbour.  ``out``: a preallocated ``cell_id``.
+    CPU tensors: PyTorch with the same arithmetic."""
+    n, ldp, _ = _geo_args("cells_bin", pos, D, None)
+    D = int(D)
+    _batch_args("cells_bin", n, gptr, seg_id)
+    G = gptr.numel() - 1
+    _cells_tables("cells_bin", G, glo, gn, pos.is_cuda)
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=pos.device)
+    if checks.enabled():
+        checks.rows(out, n, "cells_bin out")
+    if n == 0:
+        return out
+    if pos.is_cuda:
+        _seg_gpu_operands("cells_bin", (("gptr", gptr), ("seg_id", seg_id), ("out", out)), (), ())
+        native.hip().gnn_cells_bin(pos.data_ptr(), gptr.data_ptr(), seg_id.data_ptr(), glo.data_ptr(), gn.data_ptr(),
+                                   out.data_ptr(), n, G, D, ldp, _st(pos))
+        return out
+    at = _acc_dtype(pos.dtype)
+    s = seg_id.long()
+    sc = s.clamp(0, G - 1)
+    g0 = gptr.long().clamp(0, n)[sc]
+    g1 = torch.maximum(gptr.long().clamp(0, n)[sc + 1], g0)
+    i = torch.arange(n)
+    p = pos[:, :D].to(at)
+    ok = (s >= 0) & (s < G) & (i >= g0) & (i < g1) & torch.isfinite(p).all(1)
+    v = (torch.where(ok[:, None], p, torch.zeros_like(p)) - glo[sc, :D].to(at)) * glo[sc, 3:3 + D].to(at)
+    v = torch.nan_to_num(v, nan=0.0)                          # inf * 0 on an axis of one cell: bin 0 either way
+    idx = torch.zeros(n, dtype=torch.int64)
+    for a in range(D):
+        na = gn[sc, a].long().clamp(1, CELLS_NA_MAX)
+        b = torch.minimum(v[:, a].clamp(0, CELLS_NA_MAX).long(), na - 1)
+        idx = idx * na + b
+    cell = g0 + sc + torch.minimum(idx, (g1 - g0 - 1).clamp(min=0))
+    out[:n] = torch.where(ok, cell, torch.full_like(cell, n + G)).to(torch.int32)
+    return out
+
+
+def cells_order(pos, D, cell_id, G):
+    """The points in cell order, device plumbing in PyTorch (a stable sort, so ids ascend inside
+    a cell): ``(perm, scell, cptr, spos)`` -- ``perm`` int32 ``[n]`` the point at each sorted
+    position, ``scell`` int32 ``[n]`` its cell, ``cptr`` int32 ``[n + G + 2]`` the first sorted
+    position of every cell id (cell c holds the positions ``[cptr[c], cptr[c+1])``; the last
+    entry is ``n``), ``spos`` ``[n, 4]`` the positions in that order, padded with zeros to 16
+    bytes.  No host synchronisation."""
+    n = cell_id.shape[0]
+    scell, perm = torch.sort(cell_id[:n], stable=True)
+    ids = torch.arange(n + G + 2, dtype=torch.int32, device=cell_id.device)
+    cptr = torch.searchsorted(scell, ids, out_int32=True)
+    spos = torch.zeros(n, 4, dtype=pos.dtype, device=pos.device)
+    spos[:, :D] = pos[perm, :D]
+    return perm.to(torch.int32), scell, cptr, spos
+
+
+def cells_prepare(pos, D, r, gptr, seg_id):
+    """Grid, bins and cell order in one call: ``(glo, gn, cell_id, perm, scell, cptr, spos)`` of
+    ``cells_grid``, ``cells_bin`` and ``cells_order``, what ``cells_count`` / ``cells_fill`` take."""
+    glo, gn = cells_grid(pos, D, r, gptr)
+    cell_id = cells_bin(pos, D, gptr, seg_id, glo, gn)
+    return (glo, gn, cell_id) + cells_order(pos, int(D), cell_id, gptr.numel() - 1)
+
+
+def _cells_search_args(what, spos, perm, scell, cptr, gptr, seg_id, gn, D, r, lanes):
+    n, ldp, lanes, r = _radius_args(what, spos, D, r, gptr, seg_id, lanes)
+    G = gptr.numel() - 1
+    if ldp != 4:
+        raise ValueError("%s: spos must be [n, 4] (cells_order), got %s" % (what, tuple(spos.shape)))
+    if perm.shape != (n,) or scell.shape != (n,) or cptr.shape != (n + G + 2,) or gn.shape != (G, 4):
+        raise ValueError("%s: perm / scell [%d], cptr [%d] and gn [%d, 4] expected, got %s, %s, %s, %s"
+                         % (what, n, n + G + 2, G, tuple(perm.shape), tuple(scell.shape), tuple(cptr.shape),
+                            tuple(gn.shape)))
+    if spos.is_cuda:
+        _seg_gpu_operands(what, (("perm", perm), ("scell", scell), ("cptr", cptr), ("gptr", gptr), ("seg_id", seg_id),
+                                 ("gn", gn)), (), ())
+    return n, G, lanes, r
+
+
+def _cells_cpu(spos, perm, scell, cptr, gptr, seg_id, gn, D, r, loop):
+    """(deg, col, d2) of the radius graph through the cells on the CPU: every row walks the up
+    to 3^D cells around its own, the kept pairs are then ordered by (row, source id)."""
+    n = perm.numel()
+    G = gptr.numel() - 1
+    at = _acc_dtype(spos.dtype)
+    r2 = torch.tensor(r, dtype=at) * torch.tensor(r, dtype=at)
+    k = torch.arange(n)
+    pm = perm.long()
+    c = scell.long()
+    s = seg_id.long()[pm]
+    sc = s.clamp(0, max(G - 1, 0))
+    cb = gptr.long().clamp(0, n)[sc] + sc
+    na = gn.long()[sc, :3].clamp(1, CELLS_NA_MAX)
+    na[:, D:] = 1
+    l = c - cb
+    act = (c >= 0) & (c < n + G) & (s >= 0) & (s < G) & (l >= 0) & (l < na.prod(1))
+    l = torch.where(act, l, torch.zeros_like(l))
+    b2 = l % na[:, 2]
+    t = l // na[:, 2]
+    b = (t // na[:, 1], t % na[:, 1], b2)
+    cp = cptr.long()
+    P = spos[:, :D].to(at)
+    rows, srcs, dd = [], [], []
+    for d0 in (-1, 0, 1):
+        for d1 in (-1, 0, 1):
+            for d2 in (-1, 0, 1):
+                a = (b[0] + d0, b[1] + d1, b[2] + d2)
+                ok = act.clone()
+                for x in range(3):
+                    ok &= (a[x] >= 0) & (a[x] < na[:, x])
+                cell = torch.where(ok, cb + (a[0] * na[:, 1] + a[1]) * na[:, 2] + a[2], torch.zeros_like(cb))
+                j0 = cp[cell]
+                cnt = torch.where(ok, cp[cell + 1] - j0, torch.zeros_like(j0))
+                own = torch.repeat_interleave(k, cnt)
+                first = torch.cumsum(cnt, 0) - cnt
+                kk = j0[own] + torch.arange(own.numel()) - first[own]
+                d = _sq_dist(P[own], P[kk])
+                keep = d <= r2                                # False for NaN
+                if not loop:
+                    keep &= kk != own
+                rows.append(pm[own[keep]])
+                srcs.append(pm[kk[keep]])
+                dd.append(d[keep])
+    rows, srcs, dd = torch.cat(rows), torch.cat(srcs), torch.cat(dd)
+    order = torch.argsort(rows * max(n, 1) + srcs)
+    deg = torch.bincount(rows, minlength=n).to(torch.int32)
+    return deg, srcs[order].to(torch.int32), dd[order]
+
+
+def cells_count(spos, perm, scell, cptr, gptr, seg_id, gn, D, r, loop=False, lanes=None, out=None):
+    """The count pass of the cell-list radius search (gnn_cells.hip, cells_search_kernel):
+    ``deg[i]``, int32 ``[n]`` under the original row ids, **equal to** ``radius_count`` **for the
+    same** ``pos``, ``D``, ``r``, ``gptr``, ``seg_id`` **and** ``loop`` -- O(n) candidates instead of
+    O(n_g^2).  ``spos``, ``perm``, ``scell``, ``cptr`` come from ``cells_order`` (``cells_prepare``),
+    ``gn`` from ``cells_grid``.  The sub-group of row i walks the cells around its own, clipped at
+    the grid's edges; the cells that differ only along the last axis are one contiguous range
+    of the sorted points.  ``seg_id[i]`` must be the graph whose range holds i, or lie outside
+    ``[0, G)`` (``cells_bin``).  Non-periodic, D = 1..3, radius search only: no periodic cells, no
+    k-NN or neighbour cap on this path.  ``lanes``: force the sub-group width (8 / 16 / 32 / 64);
+    the result is the same for every width.  ``out``: a preallocated ``deg``.  CPU tensors:
+    PyTorch through the same cells."""
+    n, G, lanes, r = _cells_search_args("cells_count", spos, perm, scell, cptr, gptr, seg_id, gn, D, r, lanes)
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=spos.device)
+    if checks.enabled():
+        checks.rows(out, n, "cells_count out")
+    if n == 0:
+        return out
+    if spos.is_cuda:
+        _seg_gpu_operands("cells_count", (("out", out),), (), ())
+        native.hip().gnn_cells_count(spos.data_ptr(), perm.data_ptr(), scell.data_ptr(), cptr.data_ptr(),
+                                     gptr.data_ptr(), seg_id.data_ptr(), gn.data_ptr(), out.data_ptr(), n, G, int(D),
+                                     4, r, int(bool(loop)), lanes, _st(spos))
+        return out
+    out[:n] = _cells_cpu(spos, perm, scell, cptr, gptr, seg_id, gn, int(D), r, loop)[0]
+    return out
+
+
+def cells_fill(spos, perm, scell, cptr, gptr, seg_id, gn, D, r, rowptr, loop=False, lanes=None, out=None, d2=None,
+               with_d2=False, nnz=None, scratch=None):
+    """The fill pass of the cell-list radius search (gnn_cells.hip, cells_search_kernel with
+    stores, then cells_rows_kernel): ``col`` and, with ``with_d2`` or a ``d2`` buffer, ``d2`` **equal
+    to** ``radius_fill``'s: rows in ascending source id, nothing written at or past
+    ``rowptr[i+1]``.  The search writes every row in scan order into ``scratch = (sj, sd)`` (int32
+    and fp32, at least as long as ``out``; allocated when ``None``: the one scratch copy of the
+    edge list); the row pass ranks every entry inside its row -- ids are distinct, so the slot
+    is ``rowptr[i] + #{j' < j}`` -- and stores it there; any row length works.  No atomics: the
+    same CSR for every ``lanes``, grid and run.  Other arguments as in ``cells_count`` /
+    ``radius_fill``.  Returns ``(col, d2)``."""
+    n, G, lanes, r = _cells_search_args("cells_fill", spos, perm, scell, cptr, gptr, seg_id, gn, D, r, lanes)
+    if rowptr.dim() != 1 or rowptr.numel() != n + 1:
+        raise ValueError("cells_fill: rowptr must be [%d], got %s" % (n + 1, tuple(rowptr.shape)))
+    if out is None:
+        nnz = int(rowptr[-1]) if nnz is None else int(nnz)
+        out = torch.empty(nnz, dtype=torch.int32, device=spos.device)
+    if d2 is None and with_d2:
+        d2 = torch.empty(out.numel(), dtype=_acc_dtype(spos.dtype), device=spos.device)
+    cap = out.numel() if d2 is None else min(out.numel(), d2.numel())
+    if checks.enabled():
+        _check_ptr(rowptr, 2 ** 31 - 1, "cells_fill")
+        if cap < int(rowptr[-1]):
+            raise ValueError("CGNN_CHECK: cells_fill: the buffers hold %d edges, rowptr ends at %d"
+                             % (cap, int(rowptr[-1])))
+    if spos.is_cuda:
+        if scratch is None:
+            scratch = (torch.empty(cap, dtype=torch.int32, device=spos.device),
+                       torch.empty(cap, dtype=torch.float32, device=spos.device))
+        sj, sd = scratch
+        if sj.numel() < cap or sd.numel() < cap:
+            raise ValueError("cells_fill: the scratch holds %d / %d edges, %d needed" % (sj.numel(), sd.numel(), cap))
+        _seg_gpu_operands("cells_fill", (("rowptr", rowptr), ("out", out), ("scratch ids", sj)),
+                          (("d2", d2), ("scratch d2", sd)), ())
+        if n == 0 or cap == 0:                                # no edge to write (a null pointer)
+            return out, d2
+        h = native.hip()
+        h.gnn_cells_fill(spos.data_ptr(), perm.data_ptr(), scell.data_ptr(), cptr.data_ptr(), gptr.data_ptr(),
+                         seg_id.data_ptr(), gn.data_ptr(), rowptr.data_ptr(), sj.data_ptr(), sd.data_ptr(), n, G,
+                         int(D), 4, r, int(bool(loop)), lanes, cap, _st(spos))
+        h.gnn_cells_rows(rowptr.data_ptr(), sj.data_ptr(), sd.data_ptr(), out.data_ptr(), _ptr(d2), n, cap, 0,
+                         _st(spos))
+        return out, d2
+    if n == 0:
+        return out, d2
+    deg, col, dd = _cells_cpu(spos, perm, scell, cptr, gptr, seg_id, gn, int(D), r, loop)
+    _fill_rows(deg, col, dd, rowptr, out, d2)
+    return out, d2
 
 
 KNN_MAX = 64            # a sub-group holds one key per lane

@@ -49,16 +49,20 @@ class SchNet(torch.nn.Module):
     as ``radius_graph`` does (positions inside the cell: ``geometry.wrap_positions``); an atom then
     interacts with the lattice images of the others and of itself.
 
+    ``method``: ``radius_graph``'s -- ``"auto"`` (cell lists for large point clouds), ``"brute"`` or
+    ``"cells"``; the neighbour list, and so the energy and the forces, are the same bit for bit.
+
     Out of scope: training on forces (a double backward through ``pair_distance``), the
     gradient with respect to the cell (stress) and ``max_num_neighbors`` over periodic images."""
 
     def __init__(self, hidden: int = 128, n_filters: int = 128, n_interactions: int = 3, n_gaussians: int = 50,
                  cutoff: float = 5.0, max_z: int = 100, generator: Optional[torch.Generator] = None,
-                 max_num_neighbors: Optional[int] = None):
+                 max_num_neighbors: Optional[int] = None, method: str = "auto"):
         super().__init__()
         if hidden < 2 or n_interactions < 0 or not cutoff > 0:
             raise ValueError("SchNet: hidden >= 2, n_interactions >= 0 and cutoff > 0 expected")
         self.cutoff, self.max_z = float(cutoff), int(max_z)
+        self.method = method
         self.max_num_neighbors = None if max_num_neighbors is None else int(max_num_neighbors)
         self.embedding = torch.nn.Parameter(torch.randn(self.max_z, hidden, generator=generator))
         self.smearing = GaussianSmearing(0.0, self.cutoff, n_gaussians)
@@ -70,8 +74,10 @@ class SchNet(torch.nn.Module):
     def neighbors(self, pos: torch.Tensor, batch: Union[GraphBatch, torch.Tensor, None] = None,
                   cell: Optional[torch.Tensor] = None, pbc=True) -> GraphBatch:
         """The radius graph of the model's cutoff, capped at the ``max_num_neighbors`` nearest
-        (one host sync: ``radius_graph``); with ``cell`` the periodic one."""
-        return radius_graph(pos, self.cutoff, batch, max_num_neighbors=self.max_num_neighbors, cell=cell, pbc=pbc)
+        (one host sync: ``radius_graph``); with ``cell`` the periodic one.  The model's ``method``
+        (``"auto"`` / ``"brute"`` / ``"cells"``) goes to ``radius_graph``: the same list either way."""
+        return radius_graph(pos, self.cutoff, batch, max_num_neighbors=self.max_num_neighbors, cell=cell, pbc=pbc,
+                            method=self.method)
 
     def forward(self, z: torch.Tensor, pos: torch.Tensor, batch: Union[GraphBatch, torch.Tensor, None] = None,
                 graph: Optional[GraphBatch] = None, cell: Optional[torch.Tensor] = None, pbc=True) -> torch.Tensor:
