@@ -93,6 +93,21 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("data"), py::arg("xhat"), py::arg("noise"), py::arg("NS"), py::arg("xnorm"), py::arg("N"), py::arg("D"),
      py::arg("Dt"), py::arg("H"), py::arg("max_in"), py::arg("R"), py::arg("W"), py::arg("st"),
      py::arg("force") = -1);
+  // the forward that draws its own noise (the engine's call): noise = 0 leaves the draws unstored
+  m.def("gen_fwd_staged_draw", [](uint64_t prog, int ps, uint64_t sched, int ss, uint64_t params, int P,
+                                  uint64_t data, uint64_t xhat, uint64_t noise, int NS, uint64_t xnorm, int N, int D,
+                                  int Dt, int H, int max_in, int R, int W, uint64_t st, int force, uint64_t keys,
+                                  uint64_t step, int off, int row0) {
+    if (!keys || !step) throw std::invalid_argument("gen_fwd_staged_draw: keys and step are required");
+    chk(cgnn_launch_gen_fwd_staged_draw(Pt<const int>(prog), ps, Pt<const int>(sched), ss, Pt<const float>(params),
+                                        P, Pt<const float>(data), Pt<float>(xhat), Pt<float>(noise), NS,
+                                        Pt<float>(xnorm), N, D, Dt, H, max_in, R, W, S(st), force,
+                                        Pt<const uint32_t>(keys), Pt<const int>(step), off, row0),
+        "gen_fwd_staged_draw");
+  }, py::arg("prog"), py::arg("ps"), py::arg("sched"), py::arg("ss"), py::arg("params"), py::arg("P"),
+     py::arg("data"), py::arg("xhat"), py::arg("noise"), py::arg("NS"), py::arg("xnorm"), py::arg("N"), py::arg("D"),
+     py::arg("Dt"), py::arg("H"), py::arg("max_in"), py::arg("R"), py::arg("W"), py::arg("st"),
+     py::arg("force") = -1, py::arg("keys") = 0, py::arg("step") = 0, py::arg("off") = 0, py::arg("row0") = 0);
   m.def("gen_bwd_staged", [](uint64_t prog, int ps, uint64_t sched, int ss, uint64_t params, int P, uint64_t xhat,
                              uint64_t noise, int NS, uint64_t gradp, int nch, int R, int N, int D, int Dt, int H,
                              int max_in, int W, uint64_t gpart, uint64_t dxs, uint64_t st, int force) {
